@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- MDoF/s per V-cycle on 2-D Poisson (BASELINE.json metric), MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload at N=1: BASELINE config 3, the configuration north_star quotes the roofline target on:
 2-D Poisson 4097^2, V(2,2) weighted Jacobi (omega 0.8), 11 levels (coarsest 5x5), adaptive
 fp32 -> fp64 with switch_threshold 1e-6, f = 2 pi^2 sin(pi x) sin(pi y), u0 = 0 (synthetic).
 One step = one V-cycle of the solve loop (policy check, cycle, ||r||) with all fields resident in HBM.
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step (--dump-outputs) and prints the
+line.  --full adds the diagnostics after that: iterations to the residual floor, the roofline legs, time to solution per
+precision policy, the smoother size sweep and the CPU baselines.
 N > 1: the same workload per GPU on a px x py block decomposition (weak scaling), one process per GPU.  Started
 under torch.distributed.run the ranks come from the environment; started as plain `python bench.py --gpus N` this
 process only spawns the N ranks (before anything touches the GPU), waits and relays rank 0's line.
@@ -23,8 +26,10 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0            # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md (spec; ~6300 achievable)
+HBM_PEAK_GBS = 8000.0            # MI355X HBM3E (spec; ~6300 achievable)
 HBM_ACHIEVABLE_GBS = 6300.0
+DUMP_SAMPLE = 1 << 21            # --dump-outputs: iterate points written when the whole field exceeds DUMP_FULL_BYTES
+DUMP_FULL_BYTES = 32 << 20
 
 
 def sine_rhs(nx, ny, dtype=None):
@@ -168,6 +173,28 @@ def launch_ranks(args):
     return 0
 
 
+def dump_outputs(path, eng, r):
+    """--dump-outputs DIR: what a caller of the timed path (mg_iterate) receives after its last step, as DIR/<name>.npy:
+    residual_history (fp64, one entry per timed step), precision_codes (0 = fp32 cycle, 1 = fp64 cycle; stored as fp64)
+    and the iterate in fp64: solution (n x n) when it takes at most DUMP_FULL_BYTES, otherwise solution_sample = the
+    iterate at DUMP_SAMPLE points drawn without replacement by np.random.default_rng(0), with their row-major indices in
+    solution_sample_index (fp64, increasing).  The inputs depend on the arguments alone (sine rhs, zero start), so two
+    builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    u = eng.get_solution(np.float64)
+    arrays = {"residual_history": np.asarray(r["residual_history"], dtype=np.float64),
+              "precision_codes": np.asarray(r["precision_codes"], dtype=np.float64)}
+    if u.nbytes <= DUMP_FULL_BYTES:
+        arrays["solution"] = u
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(u.size, size=DUMP_SAMPLE, replace=False))
+        arrays["solution_sample"] = u.reshape(-1)[idx]
+        arrays["solution_sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -177,7 +204,16 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--agglomerate-at", dest="agglomerate_at", type=int, default=1025,
                     help="N > 1: levels of at most this many points per direction are solved replicated on every GPU")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="N = 1: write the outputs of the last timed step to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the timed steps also run the diagnostics (residual floor, roofline legs, time to "
+                         "solution per policy, smoother size sweep, CPU baselines); off: the headline figure only")
     args = ap.parse_args()
+    if args.gpus > 1 and args.dump_outputs:
+        ap.error("--dump-outputs writes the single-GPU line's outputs (--gpus 1)")
+    if args.gpus > 1 and args.full:
+        ap.error("--full runs the single-GPU line's diagnostics (--gpus 1); --gpus N > 1 always runs its self-check and phases")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)
@@ -189,7 +225,6 @@ def main():
         from mixed_precision_multigrid_solvers_for_pdes_amd import distributed as dist_mg
         return dist_mg.bench_main(args, rank, local_rank, world)
 
-    import numpy as np
     import torch
     assert torch.cuda.is_available(), "bench.py needs an MI355X (no CPU fallback)"
     torch.cuda.set_device(local_rank)
@@ -215,6 +250,43 @@ def main():
     hist = r["residual_history"]
     codes = r["precision_codes"]
     r0 = r["initial_residual"]
+    assert r["iterations"] == K, (r["iterations"], K)      # tol = 0: the loop cannot stop early
+    f32_cycles = sum(1 for c in codes if c == 0)
+    f64_cycles = K - f32_cycles
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, r)
+    out = {
+        "metric": "MDoF/s per V-cycle on 2D Poisson", "value": value, "unit": "MDoF/s", "n_gpus": 1, "steps": K, "warmup": W,
+        "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ("f64" if f32_cycles == 0 else "f32" if f64_cycles == 0 else "f32->f64") + " (adaptive policy)", "data": "synthetic",
+        "config": {"workload": f"2D Poisson {n}^2 adaptive fp32->fp64 (switch_threshold=1e-6), V(2,2) weighted-Jacobi "
+                               f"omega=0.8, {levels} levels, 1xMI355X", "grid": [n, n], "levels": levels,
+                   "cycle": "V(2,2)", "smoother": "jacobi", "parallelism": "1 GPU",
+                   # engine defaults of this run (include/mghip.h, mg_config): the up leg of cycle k and the down leg of cycle k + 1
+                   # of the finest level are one launch; the 5 x 5 coarsest grid is solved directly (within 1e-12 of the reference's
+                   # iteration to coarse_tol); the coarse levels from 65^2 down run in one register-resident workgroup
+                   "engine": {"speculate": int(eng.cfg.speculate), "coarse_direct": int(eng.cfg.coarse_direct), "tail": int(eng.cfg.tail),
+                              "fused": int(eng.cfg.fused)}},
+        "cycles_fp32": f32_cycles, "cycles_fp64": f64_cycles,
+        "residual_initial": r0, "residual_first": hist[0], "residual_last": hist[-1],
+        "iterations": K,
+    }
+    if args.full:
+        out.update(full_measurements(args, eng, n, K, levels, local_rank, r0, f32_cycles, f64_cycles))
+    eng.close()
+    print(json.dumps(out))
+    return 0
+
+
+def full_measurements(args, eng, n, K, levels, local_rank, r0, f32_cycles, f64_cycles):
+    """--full: the diagnostics of the line, run after the timed steps on the same engine (each resets the iterate):
+    iterations to the residual floor, the roofline legs, time to solution per precision policy, the smoother size sweep,
+    the captured reference CPU figure and the CPU baseline (unless --no-cpu-baseline).  Returns the extra keys."""
+    import numpy as np
+    import torch
+    import mixed_precision_multigrid_solvers_for_pdes_amd as mg
+    from mixed_precision_multigrid_solvers_for_pdes_amd import _lib
+
     # iterations to tolerance (north_star: "iterations-to-1e-10").  The reference's absolute, h-scaled norm cannot reach
     # 1e-10 for n >= 1025 in fp64 (SURVEY F10): an untimed 40-cycle run of the same solve gives the plateau it stalls
     # on and the cycle that reaches it, next to the relative and 1e-9 forms.
@@ -263,8 +335,6 @@ def main():
             kern[name]["span_leg_nomid"] = leg("span_leg_nomid", dtype, w, 3.5, 2.25 + 4 * 3.0 + 2.0 + 2.25)
         except Exception:
             pass                                                                     # this hierarchy runs the two-launch form
-    f32_cycles = sum(1 for c in codes if c == 0)
-    f64_cycles = K - f32_cycles
     # the timed region is mg_iterate(tol = 0, K): with a spanning leg every cycle but the first and the last is one
     # span_leg_nomid launch on level 0 (nothing can end the solve, the iterate in between is not stored)
     def level0_ms(p):
@@ -362,21 +432,7 @@ def main():
                           "stream_hbm_gbs": byts / (ms_s * 1e-3) / 1e9, "stream_frac_of_8TBs": byts / (ms_s * 1e-3) / 1e9 / HBM_PEAK_GBS})
         except Exception as exc:                          # a box without the memory for the 16385^2 rotating sets
             sweep.append({"n": m, "error": repr(exc)})
-    out = {
-        "metric": "MDoF/s per V-cycle on 2D Poisson", "value": value, "unit": "MDoF/s", "n_gpus": 1, "steps": K, "warmup": W,
-        "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": ("f64" if f32_cycles == 0 else "f32" if f64_cycles == 0 else "f32->f64") + " (adaptive policy)", "data": "synthetic",
-        "config": {"workload": f"2D Poisson {n}^2 adaptive fp32->fp64 (switch_threshold=1e-6), V(2,2) weighted-Jacobi "
-                               f"omega=0.8, {levels} levels, 1xMI355X", "grid": [n, n], "levels": levels,
-                   "cycle": "V(2,2)", "smoother": "jacobi", "parallelism": "1 GPU",
-                   # engine defaults of this run (include/mghip.h, mg_config): the up leg of cycle k and the down leg of cycle k + 1
-                   # of the finest level are one launch; the 5 x 5 coarsest grid is solved directly (within 1e-12 of the reference's
-                   # iteration to coarse_tol); the coarse levels from 65^2 down run in one register-resident workgroup
-                   "engine": {"speculate": int(eng.cfg.speculate), "coarse_direct": int(eng.cfg.coarse_direct), "tail": int(eng.cfg.tail),
-                              "fused": int(eng.cfg.fused)}},
-        "cycles_fp32": f32_cycles, "cycles_fp64": f64_cycles,
-        "residual_initial": r0, "residual_first": hist[0], "residual_last": hist[-1],
-        "iterations": K,
+    extra = {
         "iterations_to_1e-10_absolute": its_abs10, "iterations_to_1e-10_relative": its_rel, "iterations_to_1e-9_absolute": its_abs9,
         "residual_floor": floor, "iterations_to_floor": its_floor, "time_to_floor_ms": tts["adaptive"]["time_to_floor_ms"],
         "switch_reason": tts["adaptive"]["switch_reason"], "time_to_solution": tts,
@@ -389,10 +445,8 @@ def main():
         "roofline": roof,
     }
     if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(n, levels)
-    eng.close()
-    print(json.dumps(out))
-    return 0
+        extra["cpu_baseline"] = cpu_baseline(n, levels)
+    return extra
 
 
 def mg_pitch(_lib, dtype, n):
