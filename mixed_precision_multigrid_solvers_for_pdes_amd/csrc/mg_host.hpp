@@ -4,9 +4,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mghip.h"
@@ -16,6 +18,29 @@ namespace mgh {
 
 inline size_t esize(int dt) { return dt == MG_F32 ? 4 : 8; }
 inline bool valid_dtype(int dt) { return dt == MG_F32 || dt == MG_F64; }
+
+// dtype codes -> element types: calls f with a float (MG_F32) or double (anything else) value per code, so that the
+// generic lambda f names the types with decltype.  Every combination is instantiated: a site that accepts fewer rejects
+// the others with if constexpr.
+template <typename F> inline decltype(auto) with_dtype(int a, F&& f) { return a == MG_F32 ? f(float()) : f(double()); }
+template <typename F> inline decltype(auto) with_dtype(int a, int b, F&& f) {
+  return with_dtype(a, [&](auto x) -> decltype(auto) { return with_dtype(b, [&](auto y) -> decltype(auto) { return f(x, y); }); });
+}
+template <typename F> inline decltype(auto) with_dtype(int a, int b, int c, F&& f) {
+  return with_dtype(a, b, [&](auto x, auto y) -> decltype(auto) { return with_dtype(c, [&](auto z) -> decltype(auto) { return f(x, y, z); }); });
+}
+template <typename F> inline decltype(auto) with_smoother(int sm, F&& f) {
+  return sm == MG_RBGS ? f(std::integral_constant<int, mg::kSmRbgs>()) : f(std::integral_constant<int, mg::kSmJacobi>());
+}
+// fp32 interpolation (TC) only exists for an all-fp32 grid (fine T, coarse TX)
+template <typename T, typename TX, typename TC>
+constexpr bool interp_ok = !std::is_same_v<TC, float> || (std::is_same_v<T, float> && std::is_same_v<TX, float>);
+// the coarse tails' (T, TCO) = (upper levels, coarsest level and interpolation): an fp64 tail (dt) is fp64 throughout, an fp32
+// tail solves its coarsest level in the grid dtype dco.  Instantiates (double, double), (float, float), (float, double) in
+// this order, which fixes where the tail kernels sit in the code object (their calls are PC-relative).
+template <typename F> inline decltype(auto) with_tail_dtypes(int dt, int dco, F&& f) {
+  return dt == MG_F64 ? f(double(), double()) : with_dtype(dco, [&](auto co) -> decltype(auto) { return f(float(), co); });
+}
 
 struct Coef {
   double ihx2, ihy2, diag, invD;
@@ -121,6 +146,10 @@ struct mg_handle {
   std::vector<double> adapt_hist;
 
   int L() const { return (int)lv.size(); }
+  // visits of level l + 1 per visit of level l: V 1, W 2, F 2^(L-l-2) (multigrid.py:315-319)
+  int visits(int l) const {
+    return cfg.cycle == MG_CYCLE_W ? 2 : cfg.cycle == MG_CYCLE_F ? std::max(1, 1 << std::max(0, L() - l - 2)) : 1;
+  }
   // precision a level computes in (solvers/multigrid.py:275-285 + core/precision.py:337-357); the coarsest
   // level is never converted by the reference (multigrid.py:270-272 returns first) and stays in the grid dtype.
   int level_dtype_in(int l, int ph) const {

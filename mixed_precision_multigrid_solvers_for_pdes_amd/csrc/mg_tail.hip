@@ -62,12 +62,6 @@ int launch_n(mg_handle* h, const mg::Tail2Args& a, const void* rhs, void* u, boo
   }
 }
 
-template <typename T, typename TCO, typename TC>
-int launch_sm(mg_handle* h, const mg::Tail2Args& a, const void* rhs, void* u, bool zero_top, int ntop) {
-  return h->cfg.smoother == MG_RBGS ? launch_n<T, TCO, TC, mg::kSmRbgs>(h, a, rhs, u, zero_top, ntop)
-                                    : launch_n<T, TCO, TC, mg::kSmJacobi>(h, a, rhs, u, zero_top, ntop);
-}
-
 }  // namespace
 
 // The register-resident tail serves hierarchies whose last levels are the dyadic squares 65 / 33 / 17 / 9 / 5 in one
@@ -115,10 +109,7 @@ int tail2_launch(mg_handle* h, bool zero_top) {
     const Coef c = coefs(v.hx, v.hy, h->sigma);
     mg::Tail2Level& t = a.lv[l - k];
     t.ihx2 = c.ihx2; t.ihy2 = c.ihy2; t.invD = c.invD; t.diag = c.diag;
-    int reps = 1;
-    if (h->cfg.cycle == MG_CYCLE_W) reps = 2;
-    else if (h->cfg.cycle == MG_CYCLE_F) reps = std::max(1, 1 << std::max(0, L - l - 2));
-    a.reps[l - k] = reps;
+    a.reps[l - k] = h->visits(l);
     if (h->varcoef) { a.a_lv[l - k] = v.a[dt]; a.rd_lv[l - k] = v.rd[dt]; a.a_ld[l - k] = v.ld[dt]; }
   }
   {
@@ -132,11 +123,12 @@ int tail2_launch(mg_handle* h, bool zero_top) {
       a.a_lv[mg::kT2MaxLev] = v.a[dco]; a.a_ld[mg::kT2MaxLev] = v.ld[dco];
     }
   }
-  int rc;
-  if (dt == MG_F64) rc = launch_sm<double, double, double>(h, a, top.rhs[dt], top.u[dt], zero_top, h->tail2_ntop);
-  else if (dco == MG_F32) rc = launch_sm<float, float, float>(h, a, top.rhs[dt], top.u[dt], zero_top, h->tail2_ntop);
-  else rc = launch_sm<float, double, double>(h, a, top.rhs[dt], top.u[dt], zero_top, h->tail2_ntop);
-  return rc;
+  return with_tail_dtypes(dt, dco, [&](auto t, auto co) {
+    using T = decltype(t); using TCO = decltype(co);
+    return with_smoother(h->cfg.smoother, [&](auto sm) {
+      return launch_n<T, TCO, TCO, decltype(sm)::value>(h, a, top.rhs[dt], top.u[dt], zero_top, h->tail2_ntop);
+    });
+  });
 }
 
 }  // namespace mgh

@@ -82,50 +82,67 @@ inline int grid_for(long long work_items) {
 }
 
 // ------------------------------------------------------------------ typed launchers ------------
-template <typename T>
-void launch_jacobi(const void* u, const void* rhs, void* out, int nx, int ny, int ld, double hx, double hy,
-                   double omega, hipStream_t st, bool fine = false, double sigma = 0.0) {
-  if (nx < 3 || ny < 3) return;
-  const Coef c = coefs(hx, hy, sigma);
-  const mg::TileGeom g = make_geom<T>(nx, ny, ld, true);
-  auto k = c.pow2 ? (fine ? mg::jacobi_kernel<T, mg::kFineTag, false> : mg::jacobi_kernel<T, mg::kCoarseTag, false>)
-                  : (fine ? mg::jacobi_kernel<T, mg::kFineTag, true> : mg::jacobi_kernel<T, mg::kCoarseTag, true>);
-  hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, (const T*)u, (const T*)rhs, (T*)out,
-                     g, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)omega, (T)(1.0 - omega));
+bool jacobi_rb(int dt, const void* u, const void* rhs, void* out, int nx, int ny, int ld, double hx, double hy, double omega,
+               hipStream_t st, double sigma);       // the register-blocked single sweep (defined with the fused legs below)
+void d_jacobi(int dt, const void* u, const void* rhs, void* out, int nx, int ny, int ld, double hx, double hy,
+              double omega, hipStream_t st, bool fine = false, double sigma = 0.0) {
+  if (jacobi_rb(dt, u, rhs, out, nx, ny, ld, hx, hy, omega, st, sigma) || nx < 3 || ny < 3) return;
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const Coef c = coefs(hx, hy, sigma);
+    const mg::TileGeom g = make_geom<T>(nx, ny, ld, true);
+    auto k = c.pow2 ? (fine ? mg::jacobi_kernel<T, mg::kFineTag, false> : mg::jacobi_kernel<T, mg::kCoarseTag, false>)
+                    : (fine ? mg::jacobi_kernel<T, mg::kFineTag, true> : mg::jacobi_kernel<T, mg::kCoarseTag, true>);
+    hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, (const T*)u, (const T*)rhs, (T*)out,
+                       g, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)omega, (T)(1.0 - omega));
+  });
 }
-
-template <typename T>
-void launch_rbgs_colour(void* u, const void* rhs, int nx, int ny, int ld, double hx, double hy, double omega,
-                        int colour, int poff, hipStream_t st, bool fine = false, double sigma = 0.0) {
+void d_rbgs_colour(int dt, void* u, const void* rhs, int nx, int ny, int ld, double hx, double hy, double omega,
+                   int colour, int poff, hipStream_t st, bool fine = false, double sigma = 0.0) {
   if (nx < 3 || ny < 3) return;
-  const Coef c = coefs(hx, hy, sigma);
-  const mg::TileGeom g = make_geom<T>(nx, ny, ld, true);
-  auto k = c.pow2 ? (fine ? mg::rbgs_colour_kernel<T, mg::kFineTag, false> : mg::rbgs_colour_kernel<T, mg::kCoarseTag, false>)
-                  : (fine ? mg::rbgs_colour_kernel<T, mg::kFineTag, true> : mg::rbgs_colour_kernel<T, mg::kCoarseTag, true>);
-  hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, (T*)u, (const T*)rhs, g,
-                     (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)omega, (T)(1.0 - omega), colour, poff & 1);
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const Coef c = coefs(hx, hy, sigma);
+    const mg::TileGeom g = make_geom<T>(nx, ny, ld, true);
+    auto k = c.pow2 ? (fine ? mg::rbgs_colour_kernel<T, mg::kFineTag, false> : mg::rbgs_colour_kernel<T, mg::kCoarseTag, false>)
+                    : (fine ? mg::rbgs_colour_kernel<T, mg::kFineTag, true> : mg::rbgs_colour_kernel<T, mg::kCoarseTag, true>);
+    hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, (T*)u, (const T*)rhs, g,
+                       (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)omega, (T)(1.0 - omega), colour, poff & 1);
+  });
 }
 
 // returns the number of partials written (0 when NORM is off)
-template <typename T, bool WRITE_R, bool NORM>
-int launch_residual(const void* u, const void* f, void* r, double* partials, int nx, int ny, int ld, double hx,
-                    double hy, double coeff, hipStream_t st, bool fine = false, double sigma = 0.0) {
-  const Coef c = coefs(hx, hy, sigma);
-  const mg::TileGeom g = make_geom<T>(nx, ny, ld, false);
-  auto k = fine ? mg::residual_kernel<T, WRITE_R, NORM, mg::kFineTag> : mg::residual_kernel<T, WRITE_R, NORM, mg::kCoarseTag>;
-  hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, (const T*)u,
-                     (const T*)f, (T*)r, partials, g, (T)c.ihx2, (T)c.ihy2, (T)c.diag, (T)coeff);
-  return NORM ? g.ntiles : 0;
+template <bool WRITE_R, bool NORM>
+int launch_residual(int dt, const void* u, const void* f, void* r, double* partials, int nx, int ny, int ld, double hx,
+                    double hy, double coeff, hipStream_t st, bool fine, double sigma) {
+  return with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const Coef c = coefs(hx, hy, sigma);
+    const mg::TileGeom g = make_geom<T>(nx, ny, ld, false);
+    auto k = fine ? mg::residual_kernel<T, WRITE_R, NORM, mg::kFineTag> : mg::residual_kernel<T, WRITE_R, NORM, mg::kCoarseTag>;
+    hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, (const T*)u,
+                       (const T*)f, (T*)r, partials, g, (T)c.ihx2, (T)c.ihy2, (T)c.diag, (T)coeff);
+    return NORM ? g.ntiles : 0;
+  });
 }
-
-template <typename T>
-int launch_sumsq(const void* x, double* partials, int ld, int i_lo, int i_hi, int j_lo, int j_hi, hipStream_t st) {
-  const int N = mg::VecW<T>::N;
-  const long long vecs = (long long)std::max(0, i_hi - i_lo) * ((j_hi + N - 1) / N - j_lo / N);
-  const int nb = std::min(grid_for(vecs), 2048);
-  hipLaunchKernelGGL(mg::sumsq_kernel<T>, dim3(nb), dim3(mg::kBlock), 0, st, (const T*)x, partials, ld, i_lo, i_hi, j_lo,
-                     j_hi);
-  return nb;
+void d_residual(int dt, const void* u, const void* f, void* r, int nx, int ny, int ld, double hx, double hy,
+                double coeff, hipStream_t st, bool fine = false, double sigma = 0.0) {
+  launch_residual<true, false>(dt, u, f, r, nullptr, nx, ny, ld, hx, hy, coeff, st, fine, sigma);
+}
+int d_residual_norm(int dt, const void* u, const void* f, double* partials, int nx, int ny, int ld, double hx,
+                    double hy, double coeff, hipStream_t st, bool fine = false, double sigma = 0.0) {
+  return launch_residual<false, true>(dt, u, f, nullptr, partials, nx, ny, ld, hx, hy, coeff, st, fine, sigma);
+}
+int d_sumsq(int dt, const void* x, double* partials, int ld, int i_lo, int i_hi, int j_lo, int j_hi, hipStream_t st) {
+  return with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const int N = mg::VecW<T>::N;
+    const long long vecs = (long long)std::max(0, i_hi - i_lo) * ((j_hi + N - 1) / N - j_lo / N);
+    const int nb = std::min(grid_for(vecs), 2048);
+    hipLaunchKernelGGL(mg::sumsq_kernel<T>, dim3(nb), dim3(mg::kBlock), 0, st, (const T*)x, partials, ld, i_lo, i_hi, j_lo,
+                       j_hi);
+    return nb;
+  });
 }
 
 inline void launch_reduce(const double* partials, int n, double* out, hipStream_t st, mg::HostMailbox* mailbox = nullptr,
@@ -133,87 +150,16 @@ inline void launch_reduce(const double* partials, int n, double* out, hipStream_
   hipLaunchKernelGGL(mg::reduce_partials_kernel<0>, dim3(1), dim3(mg::kReduceBlock), 0, st, partials, n, out, mailbox, seq);
 }
 
-template <typename TI, typename TO>
-void launch_restrict(const void* fine, void* coarse, int ldf, int nxc, int nyc, int ldc, int sides, hipStream_t st) {
-  const int NO = mg::VecW<TO>::N;
-  hipLaunchKernelGGL((mg::restrict_fw_kernel<TI, TO>), dim3(grid_for((long long)nxc * ((nyc + NO - 1) / NO))),
-                     dim3(mg::kBlock), 0, st, (const TI*)fine, (TO*)coarse, ldf, nxc, nyc, ldc, sides);
-}
-
-template <typename TCI, typename TF, typename TC, bool ADD>
-void launch_prolong(const void* e, void* u, int nxf, int nyf, int ldf, int nxc, int nyc, int ldc, int sides,
-                    hipStream_t st) {
-  const int N = mg::VecW<TF>::N;
-  hipLaunchKernelGGL((mg::prolong_kernel<TCI, TF, TC, ADD>), dim3(grid_for((long long)nxf * ((nyf + N - 1) / N))),
-                     dim3(mg::kBlock), 0, st, (const TCI*)e, (TF*)u, nxf, nyf, ldf, nxc, nyc, ldc, sides);
-}
-
-template <typename TI, typename TO>
-void launch_convert(const void* in, void* out, int nx, int ny, int ldi, int ldo, hipStream_t st) {
-  hipLaunchKernelGGL((mg::convert_kernel<TI, TO>), dim3(grid_for((long long)nx * ny)), dim3(mg::kBlock), 0, st,
-                     (const TI*)in, (TO*)out, nx, ny, ldi, ldo);
-}
-
-template <typename T>
-void launch_coarse(void* u, const void* rhs, int nx, int ny, int ld, double hx, double hy, double coeff, double omega,
-                   double tol, int maxit, int* sweeps_dev, hipStream_t st, bool zero_init = false, const void* a = nullptr,
-                   double sigma = 0.0) {
-  const Coef c = coefs(hx, hy, sigma);
-  if (a) {          // variable coefficient: the general one-workgroup kernel
-    if (zero_init) (void)hipMemsetAsync(u, 0, (size_t)nx * ld * sizeof(T), st);
-    hipLaunchKernelGGL(mg::coarse_lexgs_kernel<T>, dim3(1), dim3(mg::kBlock), 0, st, (T*)u, (const T*)rhs, nx, ny, ld,
-                       (T)(hx * hx), (T)(hy * hy), (T)omega, (T)(1.0 - omega), (T)c.diag, (T)coeff, hx * hy, tol, maxit,
-                       sweeps_dev, (const T*)a, (T)sigma);
-    return;
-  }
-  if (nx * ny <= mg::kCoarseLdsCells) {
-    hipLaunchKernelGGL(mg::coarse_lexgs_small_kernel<T>, dim3(1), dim3(64), 0, st, (T*)u, (const T*)rhs, nx, ny, ld,
-                       (T)(hx * hx), (T)(hy * hy), (T)omega, (T)(1.0 - omega), (T)c.diag, (T)coeff, hx * hy, tol, maxit,
-                       sweeps_dev, zero_init ? 1 : 0, c.all_pow2 ? 1 : 0, sqrt_threshold(tol));
-    return;
-  }
-  if (zero_init) (void)hipMemsetAsync(u, 0, (size_t)nx * ld * sizeof(T), st);
-  hipLaunchKernelGGL(mg::coarse_lexgs_kernel<T>, dim3(1), dim3(mg::kBlock), 0, st, (T*)u, (const T*)rhs, nx, ny, ld,
-                     (T)(hx * hx), (T)(hy * hy), (T)omega, (T)(1.0 - omega), (T)c.diag, (T)coeff, hx * hy, tol,
-                     maxit, sweeps_dev, (const T*)nullptr);
-}
-
-// ------------------------------------------------------------------ dtype dispatch --------------
-bool jacobi_rb(int dt, const void* u, const void* rhs, void* out, int nx, int ny, int ld, double hx, double hy, double omega,
-               hipStream_t st, double sigma);       // the register-blocked single sweep (defined with the other launchers below)
-void d_jacobi(int dt, const void* u, const void* rhs, void* out, int nx, int ny, int ld, double hx, double hy,
-              double omega, hipStream_t st, bool fine = false, double sigma = 0.0) {
-  if (jacobi_rb(dt, u, rhs, out, nx, ny, ld, hx, hy, omega, st, sigma)) return;
-  if (dt == MG_F32) launch_jacobi<float>(u, rhs, out, nx, ny, ld, hx, hy, omega, st, fine, sigma);
-  else launch_jacobi<double>(u, rhs, out, nx, ny, ld, hx, hy, omega, st, fine, sigma);
-}
-void d_rbgs_colour(int dt, void* u, const void* rhs, int nx, int ny, int ld, double hx, double hy, double omega,
-                   int colour, int poff, hipStream_t st, bool fine = false, double sigma = 0.0) {
-  if (dt == MG_F32) launch_rbgs_colour<float>(u, rhs, nx, ny, ld, hx, hy, omega, colour, poff, st, fine, sigma);
-  else launch_rbgs_colour<double>(u, rhs, nx, ny, ld, hx, hy, omega, colour, poff, st, fine, sigma);
-}
-void d_residual(int dt, const void* u, const void* f, void* r, int nx, int ny, int ld, double hx, double hy,
-                double coeff, hipStream_t st, bool fine = false, double sigma = 0.0) {
-  if (dt == MG_F32) launch_residual<float, true, false>(u, f, r, nullptr, nx, ny, ld, hx, hy, coeff, st, fine, sigma);
-  else launch_residual<double, true, false>(u, f, r, nullptr, nx, ny, ld, hx, hy, coeff, st, fine, sigma);
-}
-int d_residual_norm(int dt, const void* u, const void* f, double* partials, int nx, int ny, int ld, double hx,
-                    double hy, double coeff, hipStream_t st, bool fine = false, double sigma = 0.0) {
-  if (dt == MG_F32) return launch_residual<float, false, true>(u, f, nullptr, partials, nx, ny, ld, hx, hy, coeff, st, fine, sigma);
-  return launch_residual<double, false, true>(u, f, nullptr, partials, nx, ny, ld, hx, hy, coeff, st, fine, sigma);
-}
-int d_sumsq(int dt, const void* x, double* partials, int ld, int i_lo, int i_hi, int j_lo, int j_hi, hipStream_t st) {
-  return dt == MG_F32 ? launch_sumsq<float>(x, partials, ld, i_lo, i_hi, j_lo, j_hi, st)
-                      : launch_sumsq<double>(x, partials, ld, i_lo, i_hi, j_lo, j_hi, st);
-}
-// whole-grid form: coarse dims follow from the fine ones and all four edges are physical boundaries
 void d_restrict_sub(int di, int dout, const void* fine, void* coarse, int ldf, int nxc, int nyc, int ldc, int sides,
                     hipStream_t st) {
-  if (di == MG_F32 && dout == MG_F32) launch_restrict<float, float>(fine, coarse, ldf, nxc, nyc, ldc, sides, st);
-  else if (di == MG_F64 && dout == MG_F64) launch_restrict<double, double>(fine, coarse, ldf, nxc, nyc, ldc, sides, st);
-  else if (di == MG_F64 && dout == MG_F32) launch_restrict<double, float>(fine, coarse, ldf, nxc, nyc, ldc, sides, st);
-  else launch_restrict<float, double>(fine, coarse, ldf, nxc, nyc, ldc, sides, st);
+  with_dtype(di, dout, [&](auto ti, auto to) {
+    using TI = decltype(ti); using TO = decltype(to);
+    const int NO = mg::VecW<TO>::N;
+    hipLaunchKernelGGL((mg::restrict_fw_kernel<TI, TO>), dim3(grid_for((long long)nxc * ((nyc + NO - 1) / NO))),
+                       dim3(mg::kBlock), 0, st, (const TI*)fine, (TO*)coarse, ldf, nxc, nyc, ldc, sides);
+  });
 }
+// whole-grid form: coarse dims follow from the fine ones and all four edges are physical boundaries
 void d_restrict(int di, int dout, const void* fine, void* coarse, int nxf, int nyf, int ldf, int ldc, hipStream_t st) {
   d_restrict_sub(di, dout, fine, coarse, ldf, (nxf - 1) / 2 + 1, (nyf - 1) / 2 + 1, ldc, mg::kAllSides, st);
 }
@@ -221,121 +167,110 @@ void d_restrict(int di, int dout, const void* fine, void* coarse, int nxf, int n
 template <bool ADD>
 int d_prolong_sub(int dc, int df, int dcomp, const void* e, void* u, int nxf, int nyf, int ldf, int nxc, int nyc, int ldc,
                   int sides, hipStream_t st) {
-  if (dcomp == MG_F32) {
-    if (dc == MG_F32 && df == MG_F32) { launch_prolong<float, float, float, ADD>(e, u, nxf, nyf, ldf, nxc, nyc, ldc, sides, st); return MG_OK; }
-    return MG_ERR_INVALID_VALUE;   // fp32 interpolation only exists for an all-fp32 grid
-  }
-  if (dc == MG_F64 && df == MG_F64) launch_prolong<double, double, double, ADD>(e, u, nxf, nyf, ldf, nxc, nyc, ldc, sides, st);
-  else if (dc == MG_F32 && df == MG_F64) launch_prolong<float, double, double, ADD>(e, u, nxf, nyf, ldf, nxc, nyc, ldc, sides, st);
-  else if (dc == MG_F64 && df == MG_F32) launch_prolong<double, float, double, ADD>(e, u, nxf, nyf, ldf, nxc, nyc, ldc, sides, st);
-  else launch_prolong<float, float, double, ADD>(e, u, nxf, nyf, ldf, nxc, nyc, ldc, sides, st);
-  return MG_OK;
+  return with_dtype(dc, df, dcomp, [&](auto tci, auto tf, auto tc) {
+    using TCI = decltype(tci); using TF = decltype(tf); using TC = decltype(tc);
+    if constexpr (!interp_ok<TF, TCI, TC>) return MG_ERR_INVALID_VALUE;
+    else {
+      const int N = mg::VecW<TF>::N;
+      hipLaunchKernelGGL((mg::prolong_kernel<TCI, TF, TC, ADD>), dim3(grid_for((long long)nxf * ((nyf + N - 1) / N))),
+                         dim3(mg::kBlock), 0, st, (const TCI*)e, (TF*)u, nxf, nyf, ldf, nxc, nyc, ldc, sides);
+      return MG_OK;
+    }
+  });
 }
 template <bool ADD>
 int d_prolong(int dc, int df, int dcomp, const void* e, void* u, int nxf, int nyf, int ldf, int ldc, hipStream_t st) {
   return d_prolong_sub<ADD>(dc, df, dcomp, e, u, nxf, nyf, ldf, (nxf - 1) / 2 + 1, (nyf - 1) / 2 + 1, ldc, mg::kAllSides, st);
 }
 void d_convert(int di, int dout, const void* in, void* out, int nx, int ny, int ldi, int ldo, hipStream_t st) {
-  if (di == MG_F32 && dout == MG_F32) launch_convert<float, float>(in, out, nx, ny, ldi, ldo, st);
-  else if (di == MG_F64 && dout == MG_F64) launch_convert<double, double>(in, out, nx, ny, ldi, ldo, st);
-  else if (di == MG_F64 && dout == MG_F32) launch_convert<double, float>(in, out, nx, ny, ldi, ldo, st);
-  else launch_convert<float, double>(in, out, nx, ny, ldi, ldo, st);
-}
-template <typename TI, typename TO>
-void launch_convert_ring(const void* in, void* out, int nx, int ny, int ldi, int ldo, hipStream_t st) {
-  hipLaunchKernelGGL((mg::convert_ring_kernel<TI, TO>), dim3(grid_for(2LL * nx + 2LL * ny)), dim3(mg::kBlock), 0, st,
-                     (const TI*)in, (TO*)out, nx, ny, ldi, ldo);
+  with_dtype(di, dout, [&](auto ti, auto to) {
+    using TI = decltype(ti); using TO = decltype(to);
+    hipLaunchKernelGGL((mg::convert_kernel<TI, TO>), dim3(grid_for((long long)nx * ny)), dim3(mg::kBlock), 0, st,
+                       (const TI*)in, (TO*)out, nx, ny, ldi, ldo);
+  });
 }
 // boundary ring of `in` -> boundary ring of `out` (the interior of `out` is left alone)
 void d_convert_ring(int di, int dout, const void* in, void* out, int nx, int ny, int ldi, int ldo, hipStream_t st) {
-  if (di == MG_F32 && dout == MG_F32) launch_convert_ring<float, float>(in, out, nx, ny, ldi, ldo, st);
-  else if (di == MG_F64 && dout == MG_F64) launch_convert_ring<double, double>(in, out, nx, ny, ldi, ldo, st);
-  else if (di == MG_F64 && dout == MG_F32) launch_convert_ring<double, float>(in, out, nx, ny, ldi, ldo, st);
-  else launch_convert_ring<float, double>(in, out, nx, ny, ldi, ldo, st);
+  with_dtype(di, dout, [&](auto ti, auto to) {
+    using TI = decltype(ti); using TO = decltype(to);
+    hipLaunchKernelGGL((mg::convert_ring_kernel<TI, TO>), dim3(grid_for(2LL * nx + 2LL * ny)), dim3(mg::kBlock), 0, st,
+                       (const TI*)in, (TO*)out, nx, ny, ldi, ldo);
+  });
 }
 void d_zero_interior(int dt, void* u, int nx, int ny, int ld, hipStream_t st) {
   if (nx < 3 || ny < 3) return;
   const long long vecs = (long long)(nx - 2) * ((ny + (int)(16 / esize(dt)) - 1) / (int)(16 / esize(dt)));
-  if (dt == MG_F32) hipLaunchKernelGGL(mg::zero_interior_kernel<float>, dim3(grid_for(vecs)), dim3(mg::kBlock), 0, st, (float*)u, nx, ny, ld);
-  else hipLaunchKernelGGL(mg::zero_interior_kernel<double>, dim3(grid_for(vecs)), dim3(mg::kBlock), 0, st, (double*)u, nx, ny, ld);
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(mg::zero_interior_kernel<T>, dim3(grid_for(vecs)), dim3(mg::kBlock), 0, st, (T*)u, nx, ny, ld);
+  });
 }
 void d_coarse(int dt, void* u, const void* rhs, int nx, int ny, int ld, double hx, double hy, double coeff,
               double omega, double tol, int maxit, int* sweeps_dev, hipStream_t st, bool zero_init = false,
               const void* a = nullptr, double sigma = 0.0) {
-  if (dt == MG_F32) launch_coarse<float>(u, rhs, nx, ny, ld, hx, hy, coeff, omega, tol, maxit, sweeps_dev, st, zero_init, a, sigma);
-  else launch_coarse<double>(u, rhs, nx, ny, ld, hx, hy, coeff, omega, tol, maxit, sweeps_dev, st, zero_init, a, sigma);
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const Coef c = coefs(hx, hy, sigma);
+    if (a) {          // variable coefficient: the general one-workgroup kernel
+      if (zero_init) (void)hipMemsetAsync(u, 0, (size_t)nx * ld * sizeof(T), st);
+      hipLaunchKernelGGL(mg::coarse_lexgs_kernel<T>, dim3(1), dim3(mg::kBlock), 0, st, (T*)u, (const T*)rhs, nx, ny, ld,
+                         (T)(hx * hx), (T)(hy * hy), (T)omega, (T)(1.0 - omega), (T)c.diag, (T)coeff, hx * hy, tol, maxit,
+                         sweeps_dev, (const T*)a, (T)sigma);
+      return;
+    }
+    if (nx * ny <= mg::kCoarseLdsCells) {
+      hipLaunchKernelGGL(mg::coarse_lexgs_small_kernel<T>, dim3(1), dim3(64), 0, st, (T*)u, (const T*)rhs, nx, ny, ld,
+                         (T)(hx * hx), (T)(hy * hy), (T)omega, (T)(1.0 - omega), (T)c.diag, (T)coeff, hx * hy, tol, maxit,
+                         sweeps_dev, zero_init ? 1 : 0, c.all_pow2 ? 1 : 0, sqrt_threshold(tol));
+      return;
+    }
+    if (zero_init) (void)hipMemsetAsync(u, 0, (size_t)nx * ld * sizeof(T), st);
+    hipLaunchKernelGGL(mg::coarse_lexgs_kernel<T>, dim3(1), dim3(mg::kBlock), 0, st, (T*)u, (const T*)rhs, nx, ny, ld,
+                       (T)(hx * hx), (T)(hy * hy), (T)omega, (T)(1.0 - omega), (T)c.diag, (T)coeff, hx * hy, tol,
+                       maxit, sweeps_dev, (const T*)nullptr);
+  });
 }
 
 
 
 // ------------------------------------------------------------------ variable coefficient ------
-template <typename T, int MODE>
-int launch_var(const void* u, const void* a, const void* f, void* out, double* partials, int nx, int ny, int ld, double hx,
-               double hy, double omega, double coeff, int colour, int poff, hipStream_t st, double sigma = 0.0) {
-  if (nx < 3 || ny < 3) return 0;
-  const Coef c = coefs(hx, hy);
-  const bool interior_only = (MODE == mg::kVarJacobi || MODE == mg::kVarRbgs);
-  const mg::TileGeom g = make_geom<T>(nx, ny, ld, interior_only);
-  hipLaunchKernelGGL((mg::varcoef_kernel<T, MODE>), dim3(g.ntiles), dim3(mg::kBlock), 0, st, (const T*)u, (const T*)a,
-                     (const T*)f, (T*)out, partials, g, (T)c.ihx2, (T)c.ihy2, (T)omega, (T)(1.0 - omega), (T)coeff, colour,
-                     poff & 1, (T)sigma);
-  return g.ntiles;
-}
 template <int MODE>
 int d_var(int dt, const void* u, const void* a, const void* f, void* out, double* partials, int nx, int ny, int ld, double hx,
           double hy, double omega, double coeff, int colour, int poff, hipStream_t st, double sigma = 0.0) {
-  return dt == MG_F32 ? launch_var<float, MODE>(u, a, f, out, partials, nx, ny, ld, hx, hy, omega, coeff, colour, poff, st, sigma)
-                      : launch_var<double, MODE>(u, a, f, out, partials, nx, ny, ld, hx, hy, omega, coeff, colour, poff, st, sigma);
-}
-template <typename TI, typename TO>
-void launch_inject(const void* fine, void* coarse, int ldf, int nxc, int nyc, int ldc, int stride, hipStream_t st) {
-  hipLaunchKernelGGL((mg::inject_kernel<TI, TO>), dim3(grid_for((long long)nxc * nyc)), dim3(mg::kBlock), 0, st,
-                     (const TI*)fine, (TO*)coarse, ldf, nxc, nyc, ldc, stride);
+  if (nx < 3 || ny < 3) return 0;
+  return with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const Coef c = coefs(hx, hy);
+    const bool interior_only = (MODE == mg::kVarJacobi || MODE == mg::kVarRbgs);
+    const mg::TileGeom g = make_geom<T>(nx, ny, ld, interior_only);
+    hipLaunchKernelGGL((mg::varcoef_kernel<T, MODE>), dim3(g.ntiles), dim3(mg::kBlock), 0, st, (const T*)u, (const T*)a,
+                       (const T*)f, (T*)out, partials, g, (T)c.ihx2, (T)c.ihy2, (T)omega, (T)(1.0 - omega), (T)coeff, colour,
+                       poff & 1, (T)sigma);
+    return g.ntiles;
+  });
 }
 void d_inject(int di, int dout, const void* fine, void* coarse, int ldf, int nxc, int nyc, int ldc, int stride, hipStream_t st) {
-  if (di == MG_F32 && dout == MG_F32) launch_inject<float, float>(fine, coarse, ldf, nxc, nyc, ldc, stride, st);
-  else if (di == MG_F64 && dout == MG_F64) launch_inject<double, double>(fine, coarse, ldf, nxc, nyc, ldc, stride, st);
-  else if (di == MG_F64 && dout == MG_F32) launch_inject<double, float>(fine, coarse, ldf, nxc, nyc, ldc, stride, st);
-  else launch_inject<float, double>(fine, coarse, ldf, nxc, nyc, ldc, stride, st);
-}
-
-template <typename T>
-void launch_rdiag(const void* a, void* rd, int nx, int ny, int ld, double hx, double hy, double sigma, hipStream_t st) {
-  const Coef c = coefs(hx, hy);
-  hipLaunchKernelGGL(mg::var_rdiag_kernel<T>, dim3(grid_for((long long)nx * ny)), dim3(mg::kBlock), 0, st, (const T*)a, (T*)rd, nx, ny, ld,
-                     (T)c.ihx2, (T)c.ihy2, (T)sigma);
+  with_dtype(di, dout, [&](auto ti, auto to) {
+    using TI = decltype(ti); using TO = decltype(to);
+    hipLaunchKernelGGL((mg::inject_kernel<TI, TO>), dim3(grid_for((long long)nxc * nyc)), dim3(mg::kBlock), 0, st,
+                       (const TI*)fine, (TO*)coarse, ldf, nxc, nyc, ldc, stride);
+  });
 }
 void d_rdiag(int dt, const void* a, void* rd, int nx, int ny, int ld, double hx, double hy, double sigma, hipStream_t st) {
-  if (dt == MG_F32) launch_rdiag<float>(a, rd, nx, ny, ld, hx, hy, sigma, st);
-  else launch_rdiag<double>(a, rd, nx, ny, ld, hx, hy, sigma, st);
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    const Coef c = coefs(hx, hy);
+    hipLaunchKernelGGL(mg::var_rdiag_kernel<T>, dim3(grid_for((long long)nx * ny)), dim3(mg::kBlock), 0, st, (const T*)a, (T*)rd, nx, ny, ld,
+                       (T)c.ihx2, (T)c.ihy2, (T)sigma);
+  });
 }
 
 // ------------------------------------------------------------------ fused legs ----------------
-struct LegGeom;
-template <typename T, int HALO, int TI>
-mg::FusedArgs fused_args(int nx, int ny, int ld, int nsweep, bool use_div, int nxc, int nyc, int ldc, int poff) {
-  using S = mg::FusedShape<T, HALO, TI>;
-  mg::FusedArgs a;
-  a.nx = nx; a.ny = ny; a.ld = ld;
-  a.nyv = std::min(ld, (ny + S::N - 1) / S::N * S::N);
-  const int tiles_i = (nx - 2 + TI - 1) / TI;
-  a.tiles_j = (ny - 1 + S::TJ - 1) / S::TJ;
-  a.ntiles = tiles_i * a.tiles_j;
-  a.nsweep = nsweep; a.nsweep2 = 0; a.band = 1; a.use_div = use_div ? 1 : 0; a.colour_offset = poff & 1;
-  a.nxc = nxc; a.nyc = nyc; a.ldc = ldc;
-  a.ci_off = a.cj_off = 0; a.sides = mg::kAllSides;
-  a.ni_lo = 1; a.ni_hi = nx - 1; a.nj_lo = 1; a.nj_hi = ny - 1;
-  a.select = 0; a.in_i_lo = a.in_j_lo = 0; a.in_i_hi = a.in_j_hi = 0;
-  static const int flags = exp_env("MG_EXP_FLAGS", 0);          // measurement builds only (mg_host.hpp: exp_env)
-  a.exp_flags = flags;
-  return a;
-}
-
 struct LegGeom {      // what every fused launch needs
-  int nx, ny, ld, nxc, nyc, ldc;
-  double hx, hy, omega, coeff;
-  int nsweep, poff;
-  bool fine;
+  int nx = 0, ny = 0, ld = 0, nxc = 0, nyc = 0, ldc = 0;
+  double hx = 0, hy = 0, omega = 0, coeff = 0;
+  int nsweep = 0, poff = 0;
+  bool fine = false;
   // sub-domain extras (defaults = whole grid)
   int ci_off = 0, cj_off = 0, sides = mg::kAllSides;
   int ni_lo = -1, ni_hi = -1, nj_lo = -1, nj_hi = -1;     // norm window; -1: the interior
@@ -345,13 +280,28 @@ struct LegGeom {      // what every fused launch needs
   const void* rdiag = nullptr;                                           // ... and its reciprocal diagonal per cell (var_rdiag_kernel)
   int rb = 0;                                                            // 1: register-blocked legs on the bandwidth-bound levels
 };
-inline void apply_sub(mg::FusedArgs& a, const LegGeom& g) {
+
+// the launch arguments of a leg whose tiles are TI rows high (the register-blocked legs re-tile them: rb_args)
+template <typename T, int HALO, int TI>
+mg::FusedArgs fused_args(const LegGeom& g, bool use_div) {
+  using S = mg::FusedShape<T, HALO, TI>;
+  mg::FusedArgs a;
+  a.nx = g.nx; a.ny = g.ny; a.ld = g.ld;
+  a.nyv = std::min(g.ld, (g.ny + S::N - 1) / S::N * S::N);
+  const int tiles_i = (g.nx - 2 + TI - 1) / TI;
+  a.tiles_j = (g.ny - 1 + S::TJ - 1) / S::TJ;
+  a.ntiles = tiles_i * a.tiles_j;
+  a.nsweep = g.nsweep; a.nsweep2 = 0; a.band = 1; a.use_div = use_div ? 1 : 0; a.colour_offset = g.poff & 1;
+  a.nxc = g.nxc; a.nyc = g.nyc; a.ldc = g.ldc;
   a.ci_off = g.ci_off; a.cj_off = g.cj_off; a.sides = g.sides;
+  a.ni_lo = 1; a.ni_hi = g.nx - 1; a.nj_lo = 1; a.nj_hi = g.ny - 1;
   if (g.ni_lo >= 0) { a.ni_lo = g.ni_lo; a.ni_hi = g.ni_hi; a.nj_lo = g.nj_lo; a.nj_hi = g.nj_hi; }
   a.select = g.select; a.in_i_lo = g.in_i_lo; a.in_i_hi = g.in_i_hi; a.in_j_lo = g.in_j_lo; a.in_j_hi = g.in_j_hi;
+  static const int flags = exp_env("MG_EXP_FLAGS", 0);          // measurement builds only (mg_host.hpp: exp_env)
+  a.exp_flags = flags;
+  return a;
 }
 
-// down leg: nsweep sweeps + residual + full-weighting restriction (interior coarse cells).  TX = coarse rhs dtype.
 // Tile height by level size: 32 rows where the launch is bandwidth-bound, 16 where it is latency-bound (<= ~1025^2).
 // Variable-coefficient red-black GS keeps 6 halo cells and the face means of every owned cell in registers: with 32-row
 // tiles that is 176 VGPRs (one workgroup per CU); 16-row tiles stay at 100 (two).
@@ -364,101 +314,18 @@ inline bool tiny_tiles(const LegGeom& g) {
   return lim > 0 && (long long)g.nx * g.ny <= lim * lim;
 }
 
-template <typename T, typename TX, int SM, int TI>
-void launch_down_ti(const void* u, const void* rhs, void* out, void* rhs_c, const LegGeom& g, bool zero_init, hipStream_t st) {
-  constexpr int HALO = 2 * mg::sweep_halo(SM) + 2;
-  const Coef c = coefs(g.hx, g.hy, g.sigma);
-  mg::FusedArgs a = fused_args<T, HALO, TI>(g.nx, g.ny, g.ld, g.nsweep, !c.pow2, g.nxc, g.nyc, g.ldc, g.poff);
-  apply_sub(a, g);
-  void (*k)(const T*, const T*, T*, const TX*, TX*, double*, mg::FusedArgs, T, T, T, T, T, T, T, const T*, T, const T*);
-  if (g.acoef) {      // variable coefficient (one symbol for all levels: TAG 0)
-    k = zero_init ? mg::fused_jacobi_kernel<T, HALO, false, mg::kPostRestrict, true, TX, T, 0, SM, TI, true>
-                  : mg::fused_jacobi_kernel<T, HALO, false, mg::kPostRestrict, false, TX, T, 0, SM, TI, true>;
-  } else if (zero_init) k = g.fine ? mg::fused_jacobi_kernel<T, HALO, false, mg::kPostRestrict, true, TX, T, 1, SM, TI>
-                                   : mg::fused_jacobi_kernel<T, HALO, false, mg::kPostRestrict, true, TX, T, 0, SM, TI>;
-  else k = g.fine ? mg::fused_jacobi_kernel<T, HALO, false, mg::kPostRestrict, false, TX, T, 1, SM, TI>
-                  : mg::fused_jacobi_kernel<T, HALO, false, mg::kPostRestrict, false, TX, T, 0, SM, TI>;
-  hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(mg::kFusedBlock), 0, st, (const T*)u, (const T*)rhs, (T*)out, (const TX*)nullptr,
-                     (TX*)rhs_c, (double*)nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)g.coeff,
-                     (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
-}
-template <typename T, typename TX, int SM>
-void launch_down(const void* u, const void* rhs, void* out, void* rhs_c, const LegGeom& g, bool zero_init, hipStream_t st) {
-  if (tiny_tiles(g)) launch_down_ti<T, TX, SM, mg::kFusedTITiny>(u, rhs, out, rhs_c, g, zero_init, st);
-  else if (small_tiles(g, SM)) launch_down_ti<T, TX, SM, mg::kFusedTISmall>(u, rhs, out, rhs_c, g, zero_init, st);
-  else launch_down_ti<T, TX, SM, mg::kFusedTI>(u, rhs, out, rhs_c, g, zero_init, st);
-}
-
-// up leg: u += P e, nsweep sweeps, optional sum of r^2 over interior cells.  TX = coarse e dtype, TC = interpolation dtype.
-// returns the number of partials (0 without norm)
-template <typename T, typename TX, typename TC, int SM, int TI>
-int launch_up_ti(const void* u, const void* rhs, void* out, const void* e_c, double* partials, const LegGeom& g, bool norm,
-                 hipStream_t st) {
-  const Coef c = coefs(g.hx, g.hy, g.sigma);
-  if (norm) {
-    constexpr int HALO = 2 * mg::sweep_halo(SM) + 1;
-    mg::FusedArgs a = fused_args<T, HALO, TI>(g.nx, g.ny, g.ld, g.nsweep, !c.pow2, g.nxc, g.nyc, g.ldc, g.poff);
-    apply_sub(a, g);
-    auto k = g.acoef ? mg::fused_jacobi_kernel<T, HALO, true, mg::kPostNorm, false, TX, TC, 0, SM, TI, true>
-           : g.fine ? mg::fused_jacobi_kernel<T, HALO, true, mg::kPostNorm, false, TX, TC, 1, SM, TI>
-                    : mg::fused_jacobi_kernel<T, HALO, true, mg::kPostNorm, false, TX, TC, 0, SM, TI>;
-    hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(mg::kFusedBlock), 0, st, (const T*)u, (const T*)rhs, (T*)out, (const TX*)e_c,
-                       (TX*)nullptr, partials, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)g.coeff,
-                       (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
-    return a.ntiles;
-  }
-  constexpr int HALO = 2 * mg::sweep_halo(SM);
-  mg::FusedArgs a = fused_args<T, HALO, TI>(g.nx, g.ny, g.ld, g.nsweep, !c.pow2, g.nxc, g.nyc, g.ldc, g.poff);
-  apply_sub(a, g);
-  auto k = g.acoef ? mg::fused_jacobi_kernel<T, HALO, true, mg::kPostNone, false, TX, TC, 0, SM, TI, true>
-         : g.fine ? mg::fused_jacobi_kernel<T, HALO, true, mg::kPostNone, false, TX, TC, 1, SM, TI>
-                  : mg::fused_jacobi_kernel<T, HALO, true, mg::kPostNone, false, TX, TC, 0, SM, TI>;
-  hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(mg::kFusedBlock), 0, st, (const T*)u, (const T*)rhs, (T*)out, (const TX*)e_c,
-                     (TX*)nullptr, (double*)nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)g.coeff,
-                     (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
-  return 0;
-}
-template <typename T, typename TX, typename TC, int SM>
-int launch_up(const void* u, const void* rhs, void* out, const void* e_c, double* partials, const LegGeom& g, bool norm,
-              hipStream_t st) {
-  if (tiny_tiles(g)) return launch_up_ti<T, TX, TC, SM, mg::kFusedTITiny>(u, rhs, out, e_c, partials, g, norm, st);
-  return small_tiles(g, SM) ? launch_up_ti<T, TX, TC, SM, mg::kFusedTISmall>(u, rhs, out, e_c, partials, g, norm, st)
-                        : launch_up_ti<T, TX, TC, SM, mg::kFusedTI>(u, rhs, out, e_c, partials, g, norm, st);
-}
-
-// plain multi-sweep smoothing (nsweep <= 2 per launch)
-template <typename T, int SM, int TI>
-void launch_sweeps_ti(const void* u, const void* rhs, void* out, const LegGeom& g, hipStream_t st) {
-  constexpr int HALO = 2 * mg::sweep_halo(SM);
-  const Coef c = coefs(g.hx, g.hy, g.sigma);
-  const mg::FusedArgs a = fused_args<T, HALO, TI>(g.nx, g.ny, g.ld, g.nsweep, !c.pow2, 0, 0, 0, g.poff);
-  auto k = g.acoef ? mg::fused_jacobi_kernel<T, HALO, false, mg::kPostNone, false, T, T, 0, SM, TI, true>
-         : g.fine ? mg::fused_jacobi_kernel<T, HALO, false, mg::kPostNone, false, T, T, 1, SM, TI>
-                  : mg::fused_jacobi_kernel<T, HALO, false, mg::kPostNone, false, T, T, 0, SM, TI>;
-  hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(mg::kFusedBlock), 0, st, (const T*)u, (const T*)rhs, (T*)out, (const T*)nullptr,
-                     (T*)nullptr, (double*)nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)0,
-                     (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
-}
-template <typename T, int SM>
-void launch_sweeps(const void* u, const void* rhs, void* out, const LegGeom& g, hipStream_t st) {
-  if (tiny_tiles(g)) launch_sweeps_ti<T, SM, mg::kFusedTITiny>(u, rhs, out, g, st);
-  else if (small_tiles(g, SM)) launch_sweeps_ti<T, SM, mg::kFusedTISmall>(u, rhs, out, g, st);
-  else launch_sweeps_ti<T, SM, mg::kFusedTI>(u, rhs, out, g, st);
-}
-
 // ---- register-blocked legs (mg_rb_kernels.hpp): constant coefficients, levels above ~1100^2 cells ------------------
 template <typename T, int HALO, int W, int RPT>
 mg::FusedArgs rb_args(const LegGeom& g, bool use_div) {
   using S = mg::RbShape<T, HALO, W, RPT>;
-  mg::FusedArgs a = fused_args<T, HALO, mg::kFusedTI>(g.nx, g.ny, g.ld, g.nsweep, use_div, g.nxc, g.nyc, g.ldc, g.poff);
+  mg::FusedArgs a = fused_args<T, HALO, mg::kFusedTI>(g, use_div);
   const int tiles_i = (g.nx - 2 + S::TI - 1) / S::TI;
   a.tiles_j = (g.ny - 1 + S::TJ - 1) / S::TJ;
   a.ntiles = tiles_i * a.tiles_j;
-  apply_sub(a, g);
   return a;
 }
 // g.rb: 0 never, 1 on levels above ~1100^2 cells (where a launch is bandwidth-bound), 2 on every level (tests)
-inline bool use_rb(const LegGeom& g, int) { return g.rb == 2 || (g.rb == 1 && (long long)g.nx * g.ny > 1100LL * 1100LL); }
+inline bool use_rb(const LegGeom& g) { return g.rb == 2 || (g.rb == 1 && (long long)g.nx * g.ny > 1100LL * 1100LL); }
 
 // Arrays of more than ~100 MB cannot stay in the 256 MiB Infinity Cache from one leg to the next (u, t and rhs compete):
 // their legs run with streaming hints (rb_leg_kernel TAG 2).  MG_RB_NT=0/1 overrides (experiments).
@@ -482,65 +349,56 @@ inline bool rb_stream(const LegGeom& g, size_t esz) {
 #ifndef MG_EXP_RB_W
 #define MG_EXP_RB_W ((SM == mg::kSmRbgs && sizeof(T) == 8) ? 8 : 4)
 #endif
-#define MG_RB_PICK(nt, ...) ((nt) ? mg::rb_leg_kernel<__VA_ARGS__, 2, SM, W, RPT, VAR> : mg::rb_leg_kernel<__VA_ARGS__, 1, SM, W, RPT, VAR>)
-template <typename T, typename TX, int SM, int W, int RPT, bool VAR>
-void launch_down_rb_s(const void* u, const void* rhs, void* out, void* rhs_c, const LegGeom& g, bool zero_init, hipStream_t st) {
-  constexpr int HALO = 2 * mg::sweep_halo(SM) + 2;
+
+// The four legs: down (nsweep sweeps + residual + full-weighting restriction to the interior coarse cells, into TX),
+// up with or without the norm (u += P e from TX with TC arithmetic, nsweep sweeps [, sum of r^2 over interior cells]), and
+// plain sweeps (nsweep <= 2 per launch).
+enum LegKind { kLegDown, kLegUpNorm, kLegUp, kLegSweeps };
+enum LegFamily { kLdsTiled, kRegBlocked };
+
+// One leg launch.  LDS-tiled: TI-row tiles, kernel by coefficient and level (variable coefficients: one symbol for all
+// levels, TAG 0).  Register-blocked: W waves x RPT rows, kernel by streaming hints.  coarse: the coarse rhs (down leg) or
+// the coarse correction (up legs).  Returns the number of norm partials (0 without the norm).
+template <int LEG, int FAM, typename T, typename TX, typename TC, int SM, int TI, int W = 0, int RPT = 0, bool VAR = false>
+int launch_leg(const void* u, const void* rhs, void* out, const void* coarse, double* partials, const LegGeom& g, bool zero_init,
+               hipStream_t st) {
+  constexpr bool PROLONG = LEG == kLegUpNorm || LEG == kLegUp;
+  constexpr int POST = LEG == kLegDown ? mg::kPostRestrict : LEG == kLegUpNorm ? mg::kPostNorm : mg::kPostNone;
+  constexpr int HALO = 2 * mg::sweep_halo(SM) + (LEG == kLegDown ? 2 : LEG == kLegUpNorm ? 1 : 0);
   const Coef c = coefs(g.hx, g.hy, g.sigma);
-  const mg::FusedArgs a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
-  const bool nt = rb_stream(g, sizeof(T));
-  auto k = zero_init ? MG_RB_PICK(nt, T, HALO, false, mg::kPostRestrict, true, TX, T)
-                     : MG_RB_PICK(nt, T, HALO, false, mg::kPostRestrict, false, TX, T);
-  hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(W * 64), 0, st, (const T*)u, (const T*)rhs, (T*)out, (const TX*)nullptr, (TX*)rhs_c,
-                     (double*)nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)g.coeff,
-                     (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
+  mg::FusedArgs a;
+  if constexpr (FAM == kRegBlocked) a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
+  else a = fused_args<T, HALO, TI>(g, !c.pow2);
+  const bool nt = FAM == kRegBlocked && rb_stream(g, sizeof(T));
+  auto pick = [&](auto zero) {
+    constexpr bool Z = decltype(zero)::value;
+    if constexpr (FAM == kRegBlocked) {
+      return nt ? mg::rb_leg_kernel<T, HALO, PROLONG, POST, Z, TX, TC, 2, SM, W, RPT, VAR>
+                : mg::rb_leg_kernel<T, HALO, PROLONG, POST, Z, TX, TC, 1, SM, W, RPT, VAR>;
+    } else {
+      return g.acoef ? mg::fused_jacobi_kernel<T, HALO, PROLONG, POST, Z, TX, TC, 0, SM, TI, true>
+           : g.fine ? mg::fused_jacobi_kernel<T, HALO, PROLONG, POST, Z, TX, TC, 1, SM, TI>
+                    : mg::fused_jacobi_kernel<T, HALO, PROLONG, POST, Z, TX, TC, 0, SM, TI>;
+    }
+  };
+  auto k = pick(std::false_type());
+  if constexpr (LEG == kLegDown) if (zero_init) k = pick(std::true_type());
+  hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(FAM == kRegBlocked ? W * 64 : mg::kFusedBlock), 0, st, (const T*)u, (const T*)rhs,
+                     (T*)out, PROLONG ? (const TX*)coarse : nullptr, POST == mg::kPostRestrict ? (TX*)coarse : nullptr,
+                     POST == mg::kPostNorm ? partials : nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)g.omega,
+                     (T)(1.0 - g.omega), (T)(LEG == kLegSweeps ? 0.0 : g.coeff), (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
+  return POST == mg::kPostNorm ? a.ntiles : 0;
 }
-template <typename T, typename TX, typename TC, int SM, int W, int RPT, bool VAR>
-int launch_up_rb_s(const void* u, const void* rhs, void* out, const void* e_c, double* partials, const LegGeom& g, bool norm, hipStream_t st) {
-  const Coef c = coefs(g.hx, g.hy, g.sigma);
-  const bool nt = rb_stream(g, sizeof(T));
-  if (norm) {
-    constexpr int HALO = 2 * mg::sweep_halo(SM) + 1;
-    const mg::FusedArgs a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
-    auto k = MG_RB_PICK(nt, T, HALO, true, mg::kPostNorm, false, TX, TC);
-    hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(W * 64), 0, st,
-                       (const T*)u, (const T*)rhs, (T*)out, (const TX*)e_c, (TX*)nullptr, partials, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD,
-                       (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)g.coeff, (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
-    return a.ntiles;
-  }
-  constexpr int HALO = 2 * mg::sweep_halo(SM);
-  const mg::FusedArgs a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
-  auto k = MG_RB_PICK(nt, T, HALO, true, mg::kPostNone, false, TX, TC);
-  hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(W * 64), 0, st,
-                     (const T*)u, (const T*)rhs, (T*)out, (const TX*)e_c, (TX*)nullptr, (double*)nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD,
-                     (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)g.coeff, (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
-  return 0;
-}
-template <typename T, int SM, int W, int RPT, bool VAR>
-void launch_sweeps_rb_s(const void* u, const void* rhs, void* out, const LegGeom& g, hipStream_t st) {
-  constexpr int HALO = 2 * mg::sweep_halo(SM);
-  const Coef c = coefs(g.hx, g.hy, g.sigma);
-  const mg::FusedArgs a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
-  const bool nt = rb_stream(g, sizeof(T));
-  auto k = MG_RB_PICK(nt, T, HALO, false, mg::kPostNone, false, T, T);
-  hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(W * 64), 0, st,
-                     (const T*)u, (const T*)rhs, (T*)out, (const T*)nullptr, (T*)nullptr, (double*)nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD,
-                     (T)c.diag, (T)g.omega, (T)(1.0 - g.omega), (T)0, (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
-}
-template <typename T, typename TX, int SM>
-void launch_down_rb(const void* u, const void* rhs, void* out, void* rhs_c, const LegGeom& g, bool zero_init, hipStream_t st) {
-  if (g.acoef) launch_down_rb_s<T, TX, SM, MG_EXP_VAR_W, 4, true>(u, rhs, out, rhs_c, g, zero_init, st);
-  else launch_down_rb_s<T, TX, SM, MG_EXP_RB_W, 8, false>(u, rhs, out, rhs_c, g, zero_init, st);
-}
-template <typename T, typename TX, typename TC, int SM>
-int launch_up_rb(const void* u, const void* rhs, void* out, const void* e_c, double* partials, const LegGeom& g, bool norm, hipStream_t st) {
-  return g.acoef ? launch_up_rb_s<T, TX, TC, SM, MG_EXP_VAR_W, 4, true>(u, rhs, out, e_c, partials, g, norm, st)
-                 : launch_up_rb_s<T, TX, TC, SM, MG_EXP_RB_W, 8, false>(u, rhs, out, e_c, partials, g, norm, st);
-}
-template <typename T, int SM>
-void launch_sweeps_rb(const void* u, const void* rhs, void* out, const LegGeom& g, hipStream_t st) {
-  if (g.acoef) launch_sweeps_rb_s<T, SM, MG_EXP_VAR_W, 4, true>(u, rhs, out, g, st);
-  else launch_sweeps_rb_s<T, SM, MG_EXP_RB_W, 8, false>(u, rhs, out, g, st);
+// the family and shape of a leg by level size
+template <int LEG, typename T, typename TX, typename TC, int SM>
+int launch_leg_sized(const void* u, const void* rhs, void* out, const void* coarse, double* partials, const LegGeom& g,
+                     bool zero_init, hipStream_t st) {
+  if (use_rb(g))
+    return g.acoef ? launch_leg<LEG, kRegBlocked, T, TX, TC, SM, 0, MG_EXP_VAR_W, 4, true>(u, rhs, out, coarse, partials, g, zero_init, st)
+                   : launch_leg<LEG, kRegBlocked, T, TX, TC, SM, 0, MG_EXP_RB_W, 8, false>(u, rhs, out, coarse, partials, g, zero_init, st);
+  if (tiny_tiles(g)) return launch_leg<LEG, kLdsTiled, T, TX, TC, SM, mg::kFusedTITiny>(u, rhs, out, coarse, partials, g, zero_init, st);
+  if (small_tiles(g, SM)) return launch_leg<LEG, kLdsTiled, T, TX, TC, SM, mg::kFusedTISmall>(u, rhs, out, coarse, partials, g, zero_init, st);
+  return launch_leg<LEG, kLdsTiled, T, TX, TC, SM, mg::kFusedTI>(u, rhs, out, coarse, partials, g, zero_init, st);
 }
 
 // Spanning leg (rb_span_kernel): 8 waves x 8 rows -- the halo of two sweep sets + residual + restriction is 6 rows
@@ -563,18 +421,47 @@ int launch_span_rb(const void* u, const void* rhs, void* out_mid, void* out_next
   return a.ntiles;
 }
 // dt: dtype of the level and of the level below, dcomp: interpolation dtype.  -1: no spanning leg for this combination.
-template <int SM>
-int d_span_sm(int dt, int dcomp, const void* u, const void* rhs, void* out_mid, void* out_next, const void* e_c, void* rhs_c,
-              double* partials, const LegGeom& g, int nsweep_pre, hipStream_t st) {
-  if (dt == MG_F64 && dcomp == MG_F64) return launch_span_rb<double, double, double, SM>(u, rhs, out_mid, out_next, e_c, rhs_c, partials, g, nsweep_pre, st);
-  if (dt == MG_F32 && dcomp == MG_F64) return launch_span_rb<float, float, double, SM>(u, rhs, out_mid, out_next, e_c, rhs_c, partials, g, nsweep_pre, st);
-  if (dt == MG_F32 && dcomp == MG_F32) return launch_span_rb<float, float, float, SM>(u, rhs, out_mid, out_next, e_c, rhs_c, partials, g, nsweep_pre, st);
-  return -1;
-}
 int d_span(int dt, int dcomp, const void* u, const void* rhs, void* out_mid, void* out_next, const void* e_c, void* rhs_c,
            double* partials, const LegGeom& g, int nsweep_pre, hipStream_t st, int sm = MG_JACOBI) {
-  return sm == MG_RBGS ? d_span_sm<mg::kSmRbgs>(dt, dcomp, u, rhs, out_mid, out_next, e_c, rhs_c, partials, g, nsweep_pre, st)
-                       : d_span_sm<mg::kSmJacobi>(dt, dcomp, u, rhs, out_mid, out_next, e_c, rhs_c, partials, g, nsweep_pre, st);
+  return with_dtype(dt, dcomp, [&](auto t, auto tc) {
+    using T = decltype(t); using TC = decltype(tc);
+    if constexpr (!interp_ok<T, T, TC>) return -1;
+    else return with_smoother(sm, [&](auto s) {
+      return launch_span_rb<T, T, TC, decltype(s)::value>(u, rhs, out_mid, out_next, e_c, rhs_c, partials, g, nsweep_pre, st);
+    });
+  });
+}
+
+// dt: fine dtype, dx: coarse rhs dtype.
+void d_down(int sm, int dt, int dx, const void* u, const void* rhs, void* out, void* rhs_c, const LegGeom& g, bool zero_init,
+            hipStream_t st) {
+  with_dtype(dt, dx, [&](auto t, auto x) {
+    using T = decltype(t);
+    with_smoother(sm, [&](auto s) {
+      launch_leg_sized<kLegDown, T, decltype(x), T, decltype(s)::value>(u, rhs, out, rhs_c, nullptr, g, zero_init, st);
+    });
+  });
+}
+// dt: fine dtype, dx: coarse e dtype, dcomp: interpolation dtype.  Returns #partials, or -1 for an unsupported combination.
+int d_up(int sm, int dt, int dx, int dcomp, const void* u, const void* rhs, void* out, const void* e_c, double* partials,
+         const LegGeom& g, bool norm, hipStream_t st) {
+  return with_dtype(dt, dx, dcomp, [&](auto t, auto x, auto tc) {
+    using T = decltype(t); using TX = decltype(x); using TC = decltype(tc);
+    if constexpr (!interp_ok<T, TX, TC>) return -1;
+    else return with_smoother(sm, [&](auto s) {
+      constexpr int SM = decltype(s)::value;
+      return norm ? launch_leg_sized<kLegUpNorm, T, TX, TC, SM>(u, rhs, out, e_c, partials, g, false, st)
+                  : launch_leg_sized<kLegUp, T, TX, TC, SM>(u, rhs, out, e_c, partials, g, false, st);
+    });
+  });
+}
+void d_sweeps(int sm, int dt, const void* u, const void* rhs, void* out, const LegGeom& g, hipStream_t st) {
+  with_dtype(dt, [&](auto t) {
+    using T = decltype(t);
+    with_smoother(sm, [&](auto s) {
+      launch_leg_sized<kLegSweeps, T, T, T, decltype(s)::value>(u, rhs, out, nullptr, nullptr, g, false, st);
+    });
+  });
 }
 
 // One weighted-Jacobi sweep on a level above ~1100^2 cells: the register-blocked sweeps kernel with nsweep = 1 (same
@@ -583,87 +470,22 @@ int d_span(int dt, int dcomp, const void* u, const void* rhs, void* out_mid, voi
 bool jacobi_rb(int dt, const void* u, const void* rhs, void* out, int nx, int ny, int ld, double hx, double hy, double omega,
                hipStream_t st, double sigma) {
   static const int on = exp_env("MG_JACOBI_RB", 1);
-  LegGeom g{nx, ny, ld, 0, 0, 0, hx, hy, omega, 0.0, 1, 0, true};
+  LegGeom g;
+  g.nx = nx; g.ny = ny; g.ld = ld; g.hx = hx; g.hy = hy; g.omega = omega; g.nsweep = 1; g.fine = true;
   g.sigma = sigma; g.rb = 1;
   // only where the arrays stream from HBM (4097^2 fp64: 81 -> 78 us); Infinity-Cache-resident sweeps are faster LDS-tiled
-  if (!on || !use_rb(g, mg::kSmJacobi) || !rb_stream(g, esize(dt))) return false;
-  if (dt == MG_F32) launch_sweeps_rb<float, mg::kSmJacobi>(u, rhs, out, g, st); else launch_sweeps_rb<double, mg::kSmJacobi>(u, rhs, out, g, st);
+  if (!on || !use_rb(g) || !rb_stream(g, esize(dt))) return false;
+  d_sweeps(MG_JACOBI, dt, u, rhs, out, g, st);
   return true;
-}
-
-template <int SM>
-void d_down_sm(int dt, int dx, const void* u, const void* rhs, void* out, void* rhs_c, const LegGeom& g, bool zero_init, hipStream_t st) {
-  if (use_rb(g, SM)) {
-    if (dt == MG_F32 && dx == MG_F32) launch_down_rb<float, float, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-    else if (dt == MG_F64 && dx == MG_F64) launch_down_rb<double, double, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-    else if (dt == MG_F64 && dx == MG_F32) launch_down_rb<double, float, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-    else launch_down_rb<float, double, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-    return;
-  }
-  if (dt == MG_F32 && dx == MG_F32) launch_down<float, float, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-  else if (dt == MG_F64 && dx == MG_F64) launch_down<double, double, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-  else if (dt == MG_F64 && dx == MG_F32) launch_down<double, float, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-  else launch_down<float, double, SM>(u, rhs, out, rhs_c, g, zero_init, st);
-}
-void d_down(int sm, int dt, int dx, const void* u, const void* rhs, void* out, void* rhs_c, const LegGeom& g, bool zero_init,
-            hipStream_t st) {
-  if (sm == MG_RBGS) d_down_sm<mg::kSmRbgs>(dt, dx, u, rhs, out, rhs_c, g, zero_init, st);
-  else d_down_sm<mg::kSmJacobi>(dt, dx, u, rhs, out, rhs_c, g, zero_init, st);
-}
-// dt: fine dtype, dx: coarse e dtype, dcomp: interpolation dtype.  Returns #partials, or -1 for an unsupported combination.
-template <int SM>
-int d_up_sm(int dt, int dx, int dcomp, const void* u, const void* rhs, void* out, const void* e_c, double* partials,
-            const LegGeom& g, bool norm, hipStream_t st) {
-  if (use_rb(g, SM)) {
-    if (dcomp == MG_F32) {
-      if (dt == MG_F32 && dx == MG_F32) return launch_up_rb<float, float, float, SM>(u, rhs, out, e_c, partials, g, norm, st);
-      return -1;
-    }
-    if (dt == MG_F64 && dx == MG_F64) return launch_up_rb<double, double, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-    if (dt == MG_F64 && dx == MG_F32) return launch_up_rb<double, float, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-    if (dt == MG_F32 && dx == MG_F64) return launch_up_rb<float, double, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-    return launch_up_rb<float, float, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-  }
-  if (dcomp == MG_F32) {
-    if (dt == MG_F32 && dx == MG_F32) return launch_up<float, float, float, SM>(u, rhs, out, e_c, partials, g, norm, st);
-    return -1;
-  }
-  if (dt == MG_F64 && dx == MG_F64) return launch_up<double, double, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-  if (dt == MG_F64 && dx == MG_F32) return launch_up<double, float, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-  if (dt == MG_F32 && dx == MG_F64) return launch_up<float, double, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-  return launch_up<float, float, double, SM>(u, rhs, out, e_c, partials, g, norm, st);
-}
-int d_up(int sm, int dt, int dx, int dcomp, const void* u, const void* rhs, void* out, const void* e_c, double* partials,
-         const LegGeom& g, bool norm, hipStream_t st) {
-  return sm == MG_RBGS ? d_up_sm<mg::kSmRbgs>(dt, dx, dcomp, u, rhs, out, e_c, partials, g, norm, st)
-                       : d_up_sm<mg::kSmJacobi>(dt, dx, dcomp, u, rhs, out, e_c, partials, g, norm, st);
-}
-void d_sweeps(int sm, int dt, const void* u, const void* rhs, void* out, const LegGeom& g, hipStream_t st) {
-  if (use_rb(g, sm == MG_RBGS ? mg::kSmRbgs : mg::kSmJacobi)) {
-    if (sm == MG_RBGS) { if (dt == MG_F32) launch_sweeps_rb<float, mg::kSmRbgs>(u, rhs, out, g, st); else launch_sweeps_rb<double, mg::kSmRbgs>(u, rhs, out, g, st); }
-    else { if (dt == MG_F32) launch_sweeps_rb<float, mg::kSmJacobi>(u, rhs, out, g, st); else launch_sweeps_rb<double, mg::kSmJacobi>(u, rhs, out, g, st); }
-    return;
-  }
-  if (sm == MG_RBGS) {
-    if (dt == MG_F32) launch_sweeps<float, mg::kSmRbgs>(u, rhs, out, g, st); else launch_sweeps<double, mg::kSmRbgs>(u, rhs, out, g, st);
-  } else {
-    if (dt == MG_F32) launch_sweeps<float, mg::kSmJacobi>(u, rhs, out, g, st); else launch_sweeps<double, mg::kSmJacobi>(u, rhs, out, g, st);
-  }
-}
-
-template <typename TI, typename TO>
-void launch_inject_ring(const void* fine, void* coarse, int nxf, int nyf, int ldf, int nxc, int nyc, int ldc, int sides, int ci_off,
-                        int cj_off, hipStream_t st) {
-  hipLaunchKernelGGL((mg::inject_ring_kernel<TI, TO>), dim3(grid_for(2 * (nxc + nyc))), dim3(mg::kBlock), 0, st,
-                     (const TI*)fine, (TO*)coarse, nxf, nyf, ldf, nxc, nyc, ldc, sides, ci_off, cj_off);
 }
 
 void d_inject_ring(int di, int dout, const void* fine, void* coarse, int nxf, int nyf, int ldf, int nxc, int nyc, int ldc,
                    hipStream_t st, int sides = mg::kAllSides, int ci_off = 0, int cj_off = 0) {
-  if (di == MG_F32 && dout == MG_F32) launch_inject_ring<float, float>(fine, coarse, nxf, nyf, ldf, nxc, nyc, ldc, sides, ci_off, cj_off, st);
-  else if (di == MG_F64 && dout == MG_F64) launch_inject_ring<double, double>(fine, coarse, nxf, nyf, ldf, nxc, nyc, ldc, sides, ci_off, cj_off, st);
-  else if (di == MG_F64 && dout == MG_F32) launch_inject_ring<double, float>(fine, coarse, nxf, nyf, ldf, nxc, nyc, ldc, sides, ci_off, cj_off, st);
-  else launch_inject_ring<float, double>(fine, coarse, nxf, nyf, ldf, nxc, nyc, ldc, sides, ci_off, cj_off, st);
+  with_dtype(di, dout, [&](auto ti, auto to) {
+    using TI = decltype(ti); using TO = decltype(to);
+    hipLaunchKernelGGL((mg::inject_ring_kernel<TI, TO>), dim3(grid_for(2 * (nxc + nyc))), dim3(mg::kBlock), 0, st,
+                       (const TI*)fine, (TO*)coarse, nxf, nyf, ldf, nxc, nyc, ldc, sides, ci_off, cj_off);
+  });
 }
 
 // ------------------------------------------------------------------ host <-> device helpers -----
@@ -704,6 +526,19 @@ namespace {
 // cfg.fused: 0 one launch per operator, 1 LDS-tiled fused legs, 2 register-blocked legs on the large levels (LDS-tiled
 // below), 3 register-blocked legs on every level
 inline int rb_mode(const mg_handle* h) { return h->cfg.fused == 2 ? 1 : (h->cfg.fused == 3 ? 2 : 0); }
+
+// the fused-leg geometry of level l (dtype dt) with level l + 1 (dtype dc) below it; dc < 0: no coarse level (sweeps)
+LegGeom leg_geom(const mg_handle* h, int l, int dt, int dc) {
+  const Level& f = h->lv[l];
+  LegGeom g;
+  g.nx = f.nx; g.ny = f.ny; g.ld = f.ld[dt]; g.hx = f.hx; g.hy = f.hy;
+  if (dc >= 0) { const Level& c = h->lv[l + 1]; g.nxc = c.nx; g.nyc = c.ny; g.ldc = c.ld[dc]; }
+  g.omega = h->cfg.omega; g.coeff = h->cfg.coeff; g.poff = h->cfg.colour_offset; g.fine = l == 0;
+  g.sigma = h->sigma;
+  g.rb = rb_mode(h);
+  if (h->varcoef) { g.acoef = f.a[dt]; g.rdiag = f.rd[dt]; }
+  return g;
+}
 
 // hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which a
 // hipStreamNonBlocking stream does not wait for: zero on the stream that will use the memory.
@@ -809,10 +644,7 @@ int cycle(mg_handle* h, int l) {
     d_restrict(dt, dc, f.r[dt], c.rhs[dc], f.nx, f.ny, f.ld[dt], c.ld[dc], h->stream);
   }
   (void)hipMemsetAsync(c.u[dc], 0, (size_t)c.nx * c.ld[dc] * esize(dc), h->stream);
-  int reps = 1;
-  if (h->cfg.cycle == MG_CYCLE_W) reps = 2;
-  else if (h->cfg.cycle == MG_CYCLE_F) reps = std::max(1, 1 << std::max(0, L - l - 2));   // multigrid.py:315-319
-  for (int k = 0; k < reps; ++k) {
+  for (int k = 0, n = h->visits(l); k < n; ++k) {
     const int rc = cycle(h, l + 1);
     if (rc != MG_OK) return rc;
   }
@@ -844,10 +676,7 @@ void tail_schedule(const mg_handle* h, int k, int l, int zero_flag, std::vector<
   const int L = h->L();
   if (l == L - 1) { ops.push_back(mg::kTailSolve | ((l - k) << 8) | (zero_flag << 16)); return; }
   ops.push_back(mg::kTailDown | ((l - k) << 8) | (zero_flag << 16));
-  int reps = 1;
-  if (h->cfg.cycle == MG_CYCLE_W) reps = 2;
-  else if (h->cfg.cycle == MG_CYCLE_F) reps = std::max(1, 1 << std::max(0, L - l - 2));
-  for (int r = 0; r < reps; ++r) tail_schedule(h, k, l + 1, r == 0 ? 1 : 0, ops);
+  for (int r = 0, n = h->visits(l); r < n; ++r) tail_schedule(h, k, l + 1, r == 0 ? 1 : 0, ops);
   ops.push_back(mg::kTailUp | ((l - k) << 8));
 }
 
@@ -1021,13 +850,12 @@ int launch_tail(mg_handle* h, bool zero_top) {
   off += (size_t)mg::kPipeCells * mg::kPipeSlots * esize(dco);
   Level& top = h->lv[k];
   const dim3 grid(1), block(mg::kTailBlock);
-#define MG_TAIL_LAUNCH(T, TCO, TC, VAR)                                                                                     \
-  hipLaunchKernelGGL((mg::coarse_tail_kernel<T, TCO, TC, VAR>), grid, block, off, h->stream, (const T*)top.rhs[dt], (T*)top.u[dt], \
-                     h->d_tail_ops, a, zero_top ? 1 : 0, h->d_int)
-  if (dt == MG_F64) { if (var) MG_TAIL_LAUNCH(double, double, double, true); else MG_TAIL_LAUNCH(double, double, double, false); }
-  else if (dco == MG_F32) { if (var) MG_TAIL_LAUNCH(float, float, float, true); else MG_TAIL_LAUNCH(float, float, float, false); }
-  else { if (var) MG_TAIL_LAUNCH(float, double, double, true); else MG_TAIL_LAUNCH(float, double, double, false); }
-#undef MG_TAIL_LAUNCH
+  with_tail_dtypes(dt, dco, [&](auto t, auto co) {
+    using T = decltype(t); using TCO = decltype(co);
+    auto k = var ? mg::coarse_tail_kernel<T, TCO, TCO, true> : mg::coarse_tail_kernel<T, TCO, TCO, false>;
+    hipLaunchKernelGGL(k, grid, block, off, h->stream, (const T*)top.rhs[dt], (T*)top.u[dt], h->d_tail_ops, a, zero_top ? 1 : 0,
+                       h->d_int);
+  });
   return MG_OK;
 }
 
@@ -1057,10 +885,7 @@ int cycle_fused(mg_handle* h, int l, bool zero_u, int part = kPartFull) {
   const int dc = h->level_dtype(l + 1);
   const bool fine = (l == 0);
   const int sm = h->cfg.smoother;
-  LegGeom g{f.nx, f.ny, f.ld[dt], c.nx, c.ny, c.ld[dc], f.hx, f.hy, h->cfg.omega, h->cfg.coeff, 0, h->cfg.colour_offset, fine};
-  g.sigma = h->sigma;
-  g.rb = rb_mode(h);
-  if (h->varcoef) { g.acoef = f.a[dt]; g.rdiag = f.rd[dt]; }
+  LegGeom g = leg_geom(h, l, dt, dc);
   if (part != kPartBack) {
     StageTimer tm(h, &f, 0);
     int extra = std::max(0, h->cfg.pre - 2);
@@ -1075,10 +900,7 @@ int cycle_fused(mg_handle* h, int l, bool zero_u, int part = kPartFull) {
     d_down(sm, dt, dc, f.u[dt], f.rhs[dt], f.t[dt], c.rhs[dc], g, zero_u, h->stream);
     std::swap(f.u[dt], f.t[dt]);
   }
-  int reps = 1;
-  if (h->cfg.cycle == MG_CYCLE_W) reps = 2;
-  else if (h->cfg.cycle == MG_CYCLE_F) reps = std::max(1, 1 << std::max(0, L - l - 2));
-  for (int k = 0; k < reps && part != kPartBack; ++k) {
+  for (int k = 0, n = h->visits(l); k < n && part != kPartBack; ++k) {
     const int rc = cycle_fused(h, l + 1, k == 0);
     if (rc != MG_OK) return rc;
   }
@@ -1109,14 +931,10 @@ int cycle_fused(mg_handle* h, int l, bool zero_u, int part = kPartFull) {
 bool span_ok(const mg_handle* h) {
   if (h->cfg.speculate < 2 || !h->fused() || h->L() < 3 || h->varcoef) return false;
   if (h->cfg.pre < 1 || h->cfg.pre > 2 || h->cfg.post < 1 || h->cfg.post > 2 || h->cfg.precision == MG_PREC_DEFECT) return false;
-  const Level& f = h->lv[0];
-  LegGeom g{f.nx, f.ny, 0, 0, 0, 0, f.hx, f.hy, 0, 0, 0, 0, true};
-  g.rb = rb_mode(h);
-  if (!use_rb(g, mg::kSmJacobi)) return false;                       // bandwidth-bound levels only
+  if (!use_rb(leg_geom(h, 0, h->level_dtype(0), h->level_dtype(1)))) return false;   // bandwidth-bound levels only
   return h->level_dtype(0) == h->level_dtype(1) && (h->level_dtype(0) == MG_F32 || h->grid_dtype == MG_F64);
 }
 int cycle_span(mg_handle* h, bool keep_mid) {
-  const int L = h->L();
   Level& f = h->lv[0];
   Level& c = h->lv[1];
   const int dt = h->level_dtype(0), dc = h->level_dtype(1);
@@ -1129,9 +947,8 @@ int cycle_span(mg_handle* h, bool keep_mid) {
     d_convert_ring(dt, dt, f.u[dt], f.s[dt], f.nx, f.ny, f.ld[dt], f.ld[dt], h->stream);
     h->span_ring[dt] = true;
   }
-  LegGeom g{f.nx, f.ny, f.ld[dt], c.nx, c.ny, c.ld[dc], f.hx, f.hy, h->cfg.omega, h->cfg.coeff, 0, h->cfg.colour_offset, true};
-  g.sigma = h->sigma;
-  g.rb = rb_mode(h);
+  LegGeom g = leg_geom(h, 0, dt, dc);
+  g.acoef = g.rdiag = nullptr;                                       // constant coefficients only (span_ok)
   g.nsweep = h->cfg.post;
   const int n = d_span(dt, h->grid_dtype, f.u[dt], f.rhs[dt], keep_mid ? f.t[dt] : nullptr, f.s[dt], c.u[dc], c.rhs[dc], h->partials, g,
                        h->cfg.pre, h->stream, h->cfg.smoother);
@@ -1144,11 +961,7 @@ int cycle_span(mg_handle* h, bool keep_mid) {
 }
 // ... and the rest of that front part: the sub-cycle(s) below level 0 (queued after the norm reduction of the cycle before)
 int cycle_below_fine(mg_handle* h) {
-  const int L = h->L();
-  int reps = 1;
-  if (h->cfg.cycle == MG_CYCLE_W) reps = 2;
-  else if (h->cfg.cycle == MG_CYCLE_F) reps = std::max(1, 1 << std::max(0, L - 2));
-  for (int k = 0; k < reps; ++k) {
+  for (int k = 0, n = h->visits(0); k < n; ++k) {
     const int rc = cycle_fused(h, 1, k == 0);
     if (rc != MG_OK) return rc;
   }
@@ -2104,8 +1917,10 @@ int mg_time_op(mg_handle* h, int op, int level, int dtype, int reps, double* avg
         case 11: { void** b = hbm_sets.data() + 3 * (set_idx++ % nsets);       // the bare stream: same traffic, no stencil
                    const int N = (int)(16 / esize(dt)), nyv = std::min(v.ld[dt], (v.ny + N - 1) / N * N);
                    const int tiles_j = (nyv / N + 63) / 64, tiles_i = (v.nx + 15) / 16;
-                   if (dt == MG_F32) hipLaunchKernelGGL(mg::stream_triad_kernel<float>, dim3(tiles_i * tiles_j), dim3(256), 0, h->stream, (const float*)b[0], (const float*)b[1], (float*)b[2], v.nx, nyv, v.ld[dt], tiles_j);
-                   else hipLaunchKernelGGL(mg::stream_triad_kernel<double>, dim3(tiles_i * tiles_j), dim3(256), 0, h->stream, (const double*)b[0], (const double*)b[1], (double*)b[2], v.nx, nyv, v.ld[dt], tiles_j); } break;
+                   with_dtype(dt, [&](auto t) {
+                     using T = decltype(t);
+                     hipLaunchKernelGGL(mg::stream_triad_kernel<T>, dim3(tiles_i * tiles_j), dim3(256), 0, h->stream, (const T*)b[0], (const T*)b[1], (T*)b[2], v.nx, nyv, v.ld[dt], tiles_j);
+                   }); } break;
         case 0: d_jacobi(dt, v.u[dt], v.rhs[dt], v.t[dt], v.nx, v.ny, v.ld[dt], v.hx, v.hy, h->cfg.omega, h->stream, level == 0);
                 std::swap(v.u[dt], v.t[dt]); break;
         case 1: for (int c = 0; c < 2; ++c) d_rbgs_colour(dt, v.u[dt], v.rhs[dt], v.nx, v.ny, v.ld[dt], v.hx, v.hy, h->cfg.omega, c, h->cfg.colour_offset, h->stream, level == 0); break;
@@ -2118,14 +1933,14 @@ int mg_time_op(mg_handle* h, int op, int level, int dtype, int reps, double* avg
                   if (d_prolong<true>(dc, dt, h->grid_dtype, c.u[dc], v.u[dt], v.nx, v.ny, v.ld[dt], c.ld[dc], h->stream) != MG_OK) return MG_ERR_INVALID_VALUE; } break;
         case 6: { const int rc = run_cycle(h); if (rc != MG_OK) return rc; } break;
         case 7: { Level& c = h->lv[level + 1]; const int dc = c.rhs[dt] ? dt : 1 - dt;          // down leg
-                  LegGeom g{v.nx, v.ny, v.ld[dt], c.nx, c.ny, c.ld[dc], v.hx, v.hy, h->cfg.omega, h->cfg.coeff, exp_nsweep, h->cfg.colour_offset, level == 0}; g.sigma = h->sigma; g.rb = rb_mode(h); if (h->varcoef) { g.acoef = v.a[dt]; g.rdiag = v.rd[dt]; }
+                  LegGeom g = leg_geom(h, level, dt, dc); g.nsweep = exp_nsweep;
                   d_down(h->cfg.smoother, dt, dc, v.u[dt], v.rhs[dt], v.t[dt], c.rhs[dc], g, false, h->stream);
                   std::swap(v.u[dt], v.t[dt]); } break;
         case 8: { Level& c = h->lv[level + 1]; const int dc = c.u[dt] ? dt : 1 - dt;            // up leg (+ norm on level 0)
-                  LegGeom g{v.nx, v.ny, v.ld[dt], c.nx, c.ny, c.ld[dc], v.hx, v.hy, h->cfg.omega, h->cfg.coeff, exp_nsweep, h->cfg.colour_offset, level == 0}; g.sigma = h->sigma; g.rb = rb_mode(h); if (h->varcoef) { g.acoef = v.a[dt]; g.rdiag = v.rd[dt]; }
+                  LegGeom g = leg_geom(h, level, dt, dc); g.nsweep = exp_nsweep;
                   if (d_up(h->cfg.smoother, dt, dc, h->grid_dtype, v.u[dt], v.rhs[dt], v.t[dt], c.u[dc], h->partials, g, level == 0, h->stream) < 0) return MG_ERR_INVALID_VALUE;
                   std::swap(v.u[dt], v.t[dt]); } break;
-        case 9: { LegGeom g{v.nx, v.ny, v.ld[dt], 0, 0, 0, v.hx, v.hy, h->cfg.omega, h->cfg.coeff, exp_nsweep, h->cfg.colour_offset, level == 0}; g.sigma = h->sigma; g.rb = rb_mode(h); if (h->varcoef) { g.acoef = v.a[dt]; g.rdiag = v.rd[dt]; }
+        case 9: { LegGeom g = leg_geom(h, level, dt, -1); g.nsweep = exp_nsweep;
                   d_sweeps(h->cfg.smoother, dt, v.u[dt], v.rhs[dt], v.t[dt], g, h->stream);
                   std::swap(v.u[dt], v.t[dt]); } break;
         case 12: case 13: {                                                                      // spanning leg, with / without the store of the iterate in between
@@ -2253,8 +2068,9 @@ int mg_dev_down_leg_var(int smoother, int dtype, int coarse_dtype, int nx, int n
   CHECK_DEV((!acoef && !rdiag) || (acoef && rdiag && aligned16(acoef) && aligned16(rdiag)), "mg_dev_down_leg: coefficient and reciprocal diagonal come together, 16-byte aligned");
   CHECK_DEV(nx >= 3 && ny >= 3 && nxc >= 3 && nyc >= 3 && ld_ok(dtype, ny, ld) && ldc >= nyc && nsweep >= 0 && nsweep <= 2, "mg_dev_down_leg: bad shape / pitch / sweep count");
   CHECK_DEV(rhs && out && rhs_coarse && (zero_init || u) && u != out && aligned16(rhs) && aligned16(out) && (!u || aligned16(u)), "mg_dev_down_leg: bad pointer");
-  LegGeom g{nx, ny, ld, nxc, nyc, ldc, hx, hy, omega, coeff, nsweep, colour_offset, false};
-  g.ci_off = ci_off; g.cj_off = cj_off;
+  LegGeom g;
+  g.nx = nx; g.ny = ny; g.ld = ld; g.nxc = nxc; g.nyc = nyc; g.ldc = ldc; g.ci_off = ci_off; g.cj_off = cj_off;
+  g.hx = hx; g.hy = hy; g.omega = omega; g.coeff = coeff; g.nsweep = nsweep; g.poff = colour_offset;
   CHECK_DEV(select >= 0 && select <= 2 && (select == 0 || inner_rect), "mg_dev_down_leg: bad tile selection");
   if (select) { g.select = select; g.in_i_lo = inner_rect[0]; g.in_i_hi = inner_rect[1]; g.in_j_lo = inner_rect[2]; g.in_j_hi = inner_rect[3]; }
   g.acoef = acoef; g.rdiag = rdiag;
@@ -2281,8 +2097,10 @@ int mg_dev_up_leg_var(int smoother, int dtype, int coarse_dtype, int compute_dty
   CHECK_DEV((!acoef && !rdiag) || (acoef && rdiag && aligned16(acoef) && aligned16(rdiag)), "mg_dev_up_leg: coefficient and reciprocal diagonal come together, 16-byte aligned");
   CHECK_DEV(nx >= 3 && ny >= 3 && nxc >= 2 && nyc >= 2 && ld_ok(dtype, ny, ld) && ldc >= nyc && nsweep >= 0 && nsweep <= 2 && sides >= 0 && sides <= 15, "mg_dev_up_leg: bad shape / pitch / sweep count");
   CHECK_DEV(u && rhs && out && e_coarse && u != out && aligned16(u) && aligned16(rhs) && aligned16(out) && (!norm || (scratch && sumsq_dev)), "mg_dev_up_leg: bad pointer");
-  LegGeom g{nx, ny, ld, nxc, nyc, ldc, hx, hy, omega, coeff, nsweep, colour_offset, false};
-  g.ci_off = ci_off; g.cj_off = cj_off; g.sides = sides;
+  LegGeom g;
+  g.nx = nx; g.ny = ny; g.ld = ld; g.nxc = nxc; g.nyc = nyc; g.ldc = ldc; g.ci_off = ci_off; g.cj_off = cj_off;
+  g.hx = hx; g.hy = hy; g.omega = omega; g.coeff = coeff; g.nsweep = nsweep; g.poff = colour_offset;
+  g.sides = sides;
   if (norm) { g.ni_lo = ni_lo; g.ni_hi = ni_hi; g.nj_lo = nj_lo; g.nj_hi = nj_hi; }
   g.acoef = acoef; g.rdiag = rdiag;
   g.rb = 1;
@@ -2296,9 +2114,9 @@ int mg_dev_up_leg_var(int smoother, int dtype, int coarse_dtype, int compute_dty
 int mg_dev_span_leg_ok(int smoother, int dtype, int coarse_dtype, int compute_dtype, int nx, int ny) {
   if (smoother != MG_JACOBI || !valid_dtype(dtype) || coarse_dtype != dtype || !valid_dtype(compute_dtype)) return 0;
   if (dtype == MG_F64 && compute_dtype != MG_F64) return 0;
-  LegGeom g{nx, ny, 0, 0, 0, 0, 1.0, 1.0, 0, 0, 0, 0, false};
-  g.rb = 1;
-  return use_rb(g, mg::kSmJacobi) ? 1 : 0;
+  LegGeom g;
+  g.nx = nx; g.ny = ny; g.rb = 1;
+  return use_rb(g) ? 1 : 0;
 }
 
 int mg_dev_span_leg(int smoother, int dtype, int coarse_dtype, int compute_dtype, int nx, int ny, int ld, int nxc, int nyc, int ldc,
@@ -2311,8 +2129,10 @@ int mg_dev_span_leg(int smoother, int dtype, int coarse_dtype, int compute_dtype
             nsweep_pre >= 1 && nsweep_pre <= 2 && sides >= 0 && sides <= 15, "mg_dev_span_leg: bad shape / pitch / sweep count");
   CHECK_DEV(u && rhs && out_next && e_coarse && rhs_coarse && scratch && sumsq_dev && u != out_next && u != out_mid && out_mid != out_next &&
             aligned16(u) && aligned16(rhs) && aligned16(out_next) && (!out_mid || aligned16(out_mid)), "mg_dev_span_leg: bad pointer");
-  LegGeom g{nx, ny, ld, nxc, nyc, ldc, hx, hy, omega, coeff, nsweep_post, colour_offset, false};
-  g.ci_off = ci_off; g.cj_off = cj_off; g.sides = sides;
+  LegGeom g;
+  g.nx = nx; g.ny = ny; g.ld = ld; g.nxc = nxc; g.nyc = nyc; g.ldc = ldc; g.ci_off = ci_off; g.cj_off = cj_off;
+  g.hx = hx; g.hy = hy; g.omega = omega; g.coeff = coeff; g.nsweep = nsweep_post; g.poff = colour_offset;
+  g.sides = sides;
   g.ni_lo = ni_lo; g.ni_hi = ni_hi; g.nj_lo = nj_lo; g.nj_hi = nj_hi;
   g.rb = 1;
   const int n = d_span(dtype, compute_dtype, u, rhs, out_mid, out_next, e_coarse, rhs_coarse, (double*)scratch, g, nsweep_pre, (hipStream_t)stream);
