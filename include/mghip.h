@@ -273,7 +273,12 @@ int mg_dev_convert(int in_dtype, int out_dtype, int nx, int ny, int ldi, int ldo
  *             1 only the tiles whose staged region lies inside inner_rect = {i_lo, i_hi, j_lo, j_hi} (cells that need no
  *             ghost data: launch them while the halo exchange is in flight), 2 only the remaining tiles.
  *   up leg:   out = sweeps(u + P e_coarse); with norm != 0 also *sumsq_dev = sum of r^2 over cells
- *             [ni_lo, ni_hi) x [nj_lo, nj_hi) that are interior to this array (scratch >= mg_dev_scratch_bytes()). */
+ *             [ni_lo, ni_hi) x [nj_lo, nj_hi) that are interior to this array (scratch >= mg_dev_scratch_bytes()).
+ * What the legs (and mg_dev_jacobi) store of `out`: whole 16-byte vectors of rows 1 .. (pad columns beyond ny may be rewritten
+ * with what the inputs hold there).  Edge cells are stored with the fixed value they were read with (u, 0 under zero_init,
+ * u + P e_coarse in the up leg).  Row 0 is NEVER stored; the far edge -- row nx - 1, column ny - 1 -- may or may not be stored
+ * (the tiles cover rows 1 .. nx - 2 and columns 0 .. ny - 2; whether the last one reaches further depends on the shape and the
+ * kernel family).  The caller therefore keeps the edges of `out` equal to those of u, as the ping-pong partner of an iterate is. */
 int mg_dev_down_leg(int smoother, int dtype, int coarse_dtype, int nx, int ny, int ld, int nxc, int nyc, int ldc, int ci_off,
                     int cj_off, double hx, double hy, double omega, double coeff, int nsweep, int zero_init, int colour_offset,
                     const void* u, const void* rhs, void* out, void* rhs_coarse, void* stream, int select, const int* inner_rect);
@@ -296,7 +301,10 @@ int mg_dev_up_leg_var(int smoother, int dtype, int coarse_dtype, int compute_dty
 /* The spanning leg (csrc/mg_rb_kernels.hpp, rb_span_kernel): mg_dev_up_leg of cycle k (u += P e_coarse, nsweep_post sweeps,
  * sum r^2 over the window) and mg_dev_down_leg of cycle k + 1 (nsweep_pre sweeps, residual, full weighting into rhs_coarse) in
  * ONE pass over `u`: the iterate of cycle k goes to `out_mid` (may be NULL when nobody will read it), the pre-smoothed iterate of
- * cycle k + 1 to `out_next`; u, out_mid, out_next are three different arrays of one shape.  Same bits as the two calls.
+ * cycle k + 1 to `out_next`; u, out_mid, out_next are three different arrays of one shape.  Same bits as the two calls in every
+ * array (the sum of r^2 agrees to its last bits only: its partial sums are taken over other tiles), given
+ * that the edges of `out_mid` hold u + P e_coarse when the second call reads them (the iterate between the two halves never leaves
+ * the kernel here: its edges ARE those values, while row 0 and possibly the far edge of out_mid / out_next are not stored, see above).
  * Weighted Jacobi, constant coefficients, fine and coarse field of one dtype, arrays above ~1100^2 cells (what the
  * register-blocked legs serve); anything else returns MG_ERR_INVALID_VALUE and the caller issues the two legs.
  * mg_dev_span_leg_ok: 1 where the call would be accepted.  Replaces nothing upstream (the reference smooths, restricts and

@@ -31,7 +31,12 @@ class NumpyOps:
 
     def jacobi(self, u, rhs, out, lnx, lny, hx, hy, omega):
         res = O.jacobi(self._v(u, lnx, lny), self._v(rhs, lnx, lny), hx, hy, omega, 1, "vectorized")
-        self._v(out, lnx, lny)[1:-1, 1:-1] = res[1:-1, 1:-1]       # the kernel writes owned cells only
+        self._store_out(self._v(out, lnx, lny), res)               # ring cells: u's own values (see _store_out)
+
+    def _store_out(self, o, v):
+        """What a sweep kernel stores of the local result v: rows 1 .. lnx - 1 (edge cells carry the fixed values they were
+        read with); row 0 of `out` is never written."""
+        o[1:, :] = v[1:, :]
 
     def rbgs_colour(self, u, rhs, lnx, lny, hx, hy, omega, colour, offset):
         a, f = self._v(u, lnx, lny), self._v(rhs, lnx, lny)
@@ -46,9 +51,28 @@ class NumpyOps:
     def residual(self, u, f, r, lnx, lny, hx, hy, coeff):
         self._v(r, lnx, lny)[...] = O.residual(self._v(u, lnx, lny), self._v(f, lnx, lny), hx, hy, coeff)
 
+    def residual_mixed(self, u, f, r, lnx, lny, hx, hy, coeff):
+        """mg_dev_residual_f32in_f64out: fp32 iterate and rhs, fp64 residual evaluated in double"""
+        self._v(r, lnx, lny)[...] = O.residual_mixed(self._v(u, lnx, lny), self._v(f, lnx, lny), hx, hy, coeff)
+
+    def convert(self, src, dst, lnx, lny):
+        """mg_dev_convert: element-wise astype (core/precision.py:106-134)"""
+        d = self._v(dst, lnx, lny)
+        d[...] = self._v(src, lnx, lny).astype(d.dtype)
+
+    @staticmethod
+    def _sum_of_squares(w):
+        """sum of w^2 of an fp64 window (tests of the device sums override this with an exactly rounded sum)"""
+        return float(np.sum(w * w))
+
+    def _window(self, window, lnx, lny):
+        """row / column slices of a leg's norm window: [i_lo, i_hi) x [j_lo, j_hi) clipped to the interior of the array"""
+        i_lo, i_hi, j_lo, j_hi = window
+        return slice(max(i_lo, 1), max(min(i_hi, lnx - 1), max(i_lo, 1))), slice(max(j_lo, 1), max(min(j_hi, lny - 1), max(j_lo, 1)))
+
     def sumsq(self, field, i_lo, i_hi, j_lo, j_hi):
         w = field.numpy()[i_lo:i_hi, j_lo:j_hi].astype(np.float64)
-        return torch.tensor([float(np.sum(w * w))], dtype=torch.float64)
+        return torch.tensor([self._sum_of_squares(w)], dtype=torch.float64)
 
     def restrict(self, fine, coarse, lnxf, lnyf, lnxc, lnyc, sides):
         f, c = self._v(fine, lnxf, lnyf), self._v(coarse, lnxc, lnyc)
@@ -69,19 +93,8 @@ class NumpyOps:
                         c[a, b] = f[2 * a, 2 * b]
 
     def prolong_add(self, coarse, fine_u, lnxf, lnyf, lnxc, lnyc, sides):
-        e, u = self._v(coarse, lnxc, lnyc).astype(self.comp_dtype), self._v(fine_u, lnxf, lnyf)
-        i = np.arange(lnxf)[:, None]; j = np.arange(lnyf)[None, :]
-        ic, io, jc, jo = i >> 1, i & 1, j >> 1, j & 1
-        valid = (ic + io < lnxc) & (jc + jo < lnyc)
-        ic1, jc1 = np.minimum(ic + 1, lnxc - 1), np.minimum(jc + 1, lnyc - 1)
-        e00, e01, e10, e11 = e[ic, jc], e[ic, jc1], e[ic1, jc], e[ic1, jc1]
-        P = np.where((io == 0) & (jo == 0), e00,
-            np.where((io == 1) & (jo == 0), 0.5 * (e00 + e10),
-            np.where((io == 0) & (jo == 1), 0.5 * (e00 + e01), 0.25 * (((e00 + e01) + e10) + e11))))
-        if sides & SIDE_JHI:
-            P = np.where((io == 1) & (jo == 0) & (j == lnyf - 1), 0.0, P)
-        if sides & SIDE_IHI:
-            P = np.where((io == 0) & (jo == 1) & (i == lnxf - 1), 0.0, P)
+        u = self._v(fine_u, lnxf, lnyf)
+        P, valid = self._prolong_field(self._v(coarse, lnxc, lnyc), lnxf, lnyf, lnxc, lnyc, 0, 0, sides, u.dtype)
         wide = np.result_type(u.dtype, P.dtype)
         u[valid] = (u.astype(wide) + P.astype(wide)).astype(u.dtype)[valid]
 
@@ -135,7 +148,14 @@ class NumpyOps:
         return v
 
     def var_rdiag(self, a, rd, lnx, lny, hx, hy, sigma=0.0):
-        pass                      # the oracle's smoothers form 1 / D themselves (oracle/mg_oracle.py: _var_update)
+        """fl(1 / D) rounded once in the level's dtype on interior cells, 0 on the ring: the factor of O._var_update (the
+        stand-in's own sweeps form it themselves; the value is what mg_dev_var_rdiag stores)"""
+        av, out = self._v(a, lnx, lny), self._v(rd, lnx, lny)
+        ihx2, ihy2 = 1.0 / (hx * hx), 1.0 / (hy * hy)
+        aip, aim, ajp, ajm = O._faces(av)
+        D = (aip + aim) * ihx2 + (ajp + ajm) * ihy2 + sigma
+        out[...] = 0
+        out[1:-1, 1:-1] = 1.0 / D
 
     def down_leg(self, sm, u, rhs, out, rhs_c, lnx, lny, lnxc, lnyc, ci_off, cj_off, hx, hy, omega, coeff, nsweep, zero_init, poff,
                  select=0, inner=None, acoef=None, rdiag=None):
@@ -144,16 +164,21 @@ class NumpyOps:
         a = None if acoef is None else self._v(acoef, lnx, lny)
         v = np.zeros_like(f) if zero_init else self._v(u, lnx, lny).copy()
         v = self._sweeps(sm, v, f, hx, hy, omega, nsweep, poff, a)
-        self._v(out, lnx, lny)[1:, :] = v[1:, :]                    # the kernel never writes row 0
+        self._store_out(self._v(out, lnx, lny), v)                   # the kernel never writes row 0
         r = O.residual(v, f, hx, hy, coeff) if a is None else O.var_residual(v, f, a, hx, hy, coeff)
         c = self._v(rhs_c, lnxc, lnyc)
         ic = np.arange(1, lnxc - 1); jc = np.arange(1, lnyc - 1)
         fi = 2 * (ic - ci_off); fj = 2 * (jc - cj_off)
-        oki = (fi >= 1) & (fi <= lnx - 2); okj = (fj >= 1) & (fj <= lny - 2)
+        oki = self._complete(fi, lnx); okj = self._complete(fj, lny)
         I, J = np.meshgrid(fi[oki], fj[okj], indexing="ij")
         corners = ((r[I - 1, J - 1] + r[I - 1, J + 1]) + r[I + 1, J - 1]) + r[I + 1, J + 1]
         edges = ((r[I - 1, J] + r[I + 1, J]) + r[I, J - 1]) + r[I, J + 1]
         c[np.ix_(ic[oki], jc[okj])] = (1.0 / 16.0 * corners + 1.0 / 8.0 * edges) + 1.0 / 4.0 * r[I, J]
+
+    @staticmethod
+    def _complete(fi, n):
+        """coarse cells whose fine cell fi has its whole 3-point neighbourhood inside the interior of the local array"""
+        return (fi >= 1) & (fi <= n - 2)
 
     def up_leg(self, sm, u, rhs, out, e_c, lnx, lny, lnxc, lnyc, ci_off, cj_off, sides, hx, hy, omega, coeff, nsweep, poff, window=None,
                acoef=None, rdiag=None):
@@ -164,13 +189,13 @@ class NumpyOps:
         wide = np.result_type(v.dtype, P.dtype)
         v[valid] = (v.astype(wide) + P.astype(wide)).astype(v.dtype)[valid]
         v = self._sweeps(sm, v, f, hx, hy, omega, nsweep, poff, a)
-        self._v(out, lnx, lny)[1:, :] = v[1:, :]
+        self._store_out(self._v(out, lnx, lny), v)
         if window is None:
             return None
         r = O.residual(v, f, hx, hy, coeff) if a is None else O.var_residual(v, f, a, hx, hy, coeff)
-        i_lo, i_hi, j_lo, j_hi = window
-        w = r[max(i_lo, 1):min(i_hi, lnx - 1), max(j_lo, 1):min(j_hi, lny - 1)].astype(np.float64)
-        return torch.tensor([float(np.sum(w * w))], dtype=torch.float64)
+        si, sj = self._window(window, lnx, lny)
+        w = r[si, sj].astype(np.float64)
+        return torch.tensor([self._sum_of_squares(w)], dtype=torch.float64)
 
     span_min_cells = 1100 * 1100          # as the library: blocks above ~1100^2 cells (tests lower it to reach the path on small grids)
 
