@@ -1,7 +1,8 @@
 """Cycle plans of the decomposed solver (include/mghip.h, "Cycle plans").
 
-`DistributedMultigrid.cycle()` issues the same operations with the same pointers every cycle: fused legs, halo copies,
-send/recv groups, the coarse gather, the replicated engine's cycle, the norm reduction.  The first cycle runs through the
+`DistributedMultigrid.cycle()` (distributed.py; the legs are noted by its kernel provider, `HipOps` in dist_ops.py) issues
+the same operations with the same pointers every cycle: fused legs, halo copies, send/recv groups, the coarse gather, the
+replicated engine's cycle, the norm reduction.  The first cycle runs through the
 Python driver with a `PlanRecorder` attached, which notes each operation as an `mg_plan_op`; every later cycle is one
 `mg_plan_run` call that enqueues the whole list from C++ (kernels, RCCL calls, stream dependencies).  The reference has
 no working counterpart (its DistributedMultigridSolver cannot be imported); what this replaces is the

@@ -11,7 +11,8 @@ What is kept from the reference is the interface and the partitioning vocabulary
 sub-domain INDEPENDENTLY and stitches the pieces (gpu/multi_gpu.py:540-607), respectively replaces the coarse-grid
 correction by `u += 0.8 r` (gpu/multi_gpu_solver.py:574-593) -- neither is a multigrid solve of the global problem (SURVEY
 F6).  Here the SAME V/W/F-cycle as the single-GPU engine runs on a px x py block decomposition (distributed.py: fused legs
-on ghost zones, RCCL halo exchange, agglomerated coarse levels, one all-reduce for the norm), so `solve` returns the
+on ghost zones, RCCL halo exchange, agglomerated coarse levels, one all-reduce for the norm; the block bookkeeping, the
+kernel provider and the solve loop it re-exports live in dist_layout.py, dist_ops.py and dist_solve.py), so `solve` returns the
 single-GPU solver's iterate bit for bit, with the same residual history and info keys, plus `n_gpus`, `process_grid`,
 `exchanges_per_cycle` and the reference's aggregate keys.
 
