@@ -1,10 +1,13 @@
-// Host-side types shared by the translation units of libmghip.so (mghip.hip: the driver and the C ABI; mg_tail.hip: the
-// register-resident coarse tail).  Internal: nothing here is part of the C ABI (include/mghip.h).
+// Host-side types and helpers shared by the translation units of libmghip.so (mg_launch.hip: the kernel launchers;
+// mg_engine.hip: the handle and the cycle driver; mg_solve.hip: norms, precision policy and the solve loop; mg_dev.hip: the
+// stateless C ABI; mg_tail.hip: the register-resident coarse tail).  Internal: nothing here is part of the C ABI
+// (include/mghip.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <string>
@@ -15,6 +18,26 @@
 #include "mg_kernels.hpp"
 
 namespace mgh {
+
+// The thread's last error message (mg_last_error(NULL)); the one definition is in mg_engine.hip.
+std::string& last_error();
+inline int fail(std::string* where, int code, const std::string& msg) {
+  last_error() = msg;
+  if (where) *where = msg;
+  return code;
+}
+#define HIPC(errstr, call)                                                                         \
+  do {                                                                                             \
+    hipError_t e_ = (call);                                                                        \
+    if (e_ != hipSuccess)                                                                          \
+      return fail(errstr, (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? MG_ERR_NO_DEVICE : \
+                          (e_ == hipErrorOutOfMemory ? MG_ERR_ALLOC : MG_ERR_HIP),                 \
+                  std::string(#call) + ": " + hipGetErrorString(e_));                              \
+  } while (0)
+
+inline double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 inline size_t esize(int dt) { return dt == MG_F32 ? 4 : 8; }
 inline bool valid_dtype(int dt) { return dt == MG_F32 || dt == MG_F64; }
@@ -180,4 +203,26 @@ namespace mgh {
 // hierarchy (and from which level) and fills h->tail2_*; tail2_launch runs one visit of that sub-cycle on h->stream.
 int tail2_plan(mg_handle* h);
 int tail2_launch(mg_handle* h, bool zero_top);
+
+// mg_engine.hip: what the solve loop (mg_solve.hip) and the stateless ABI (mg_dev.hip) use of the handle and cycle driver.
+// hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which a
+// hipStreamNonBlocking stream does not wait for: alloc_zero zeroes on the stream that will use the memory.
+int alloc_zero(std::string* err, void** p, size_t bytes, hipStream_t st = nullptr);
+int download(std::string* err, void* host, int hdt, const void* dev, int ddt, int ld, int nx, int ny, void* staging,
+             hipStream_t st);
+int set_rhs_impl(mg_handle* h, const void* rhs, int hdt);
+int set_u_impl(mg_handle* h, const void* u0, int hdt);
+void inject_rings(mg_handle* h, int ph, bool only_shared = false);
+void inject_rings_once(mg_handle* h, int p);
+// `part` (level 0 only) splits the fused cycle for speculative launching: the FRONT part (down leg + the whole
+// sub-cycle below) never writes the buffer that holds the current fine iterate, only the BACK part (up leg) does.
+constexpr int kPartFull = 0, kPartFront = 1, kPartBack = 2;
+int cycle_fused(mg_handle* h, int l, bool zero_u, int part = kPartFull);
+bool span_ok(const mg_handle* h);
+int cycle_span(mg_handle* h, bool keep_mid);
+int cycle_below_fine(mg_handle* h);
+int fmg_init(mg_handle* h, int ncyc);
+int defect_fmg(mg_handle* h, int ncyc);
+int defect_cycle(mg_handle* h);
+int run_cycle(mg_handle* h);
 }  // namespace mgh

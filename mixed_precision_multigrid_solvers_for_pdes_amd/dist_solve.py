@@ -4,7 +4,7 @@ import math
 
 
 def stagnating(hist):
-    """should_promote_precision on the last five residual norms (core/precision.py:189-246; csrc/mghip.hip: stagnating)."""
+    """should_promote_precision on the last five residual norms (core/precision.py:189-246; csrc/mg_solve.hip: stagnating)."""
     if len(hist) < 5:
         return False
     r = hist[-5:]
@@ -19,7 +19,7 @@ def stagnating(hist):
 
 
 def fp32_phase_pays(hx, hy, domain, coeff=-1.0, sigma=0.0):
-    """csrc/mghip.hip fp32_phase_pays: the fp32 residual floor relative to ||r_0|| is at most eps32 diag(A) / lambda_min (a
+    """csrc/mg_solve.hip fp32_phase_pays: the fp32 residual floor relative to ||r_0|| is at most eps32 diag(A) / lambda_min (a
     property of the grid); with a contraction of ~0.15 per cycle the fp32 phase is good for log(that) / log(0.15) cycles, and
     it is entered only when that is at least two -- its switches cost about one cycle's saving."""
     lx, ly = domain[1] - domain[0], domain[3] - domain[2]
@@ -29,7 +29,7 @@ def fp32_phase_pays(hx, hy, domain, coeff=-1.0, sigma=0.0):
 
 
 class AdaptivePolicy:
-    """The engine's adaptive rule (csrc/mghip.hip: adapt, one-way variant of core/precision.py:270-302) as host logic
+    """The engine's adaptive rule (csrc/mg_solve.hip: adapt, one-way variant of core/precision.py:270-302) as host logic
     for drivers that hold one solver per precision: start in double, drop to single on a large first residual,
     promote for good when ||r|| < 10 thr or the fp32 iteration stagnates."""
 
@@ -43,7 +43,7 @@ class AdaptivePolicy:
         self.reason = None        # why the fp32 phase ended: "threshold" / "stagnation" / "fp32_floor"; "fp32_skipped": never begun
 
     def set_floor(self, diag, u_norm_h):
-        """after the first fp32 cycle (csrc/mghip.hip, iterate_impl): within a factor 2 of this floor another fp32 cycle
+        """after the first fp32 cycle (csrc/mg_solve.hip, measure_fp32_floor): within a factor 2 of this floor another fp32 cycle
         cannot lower the residual, and the policy promotes at once instead of waiting for the stagnation window to fill"""
         self.floor = self.EPS32 * diag * u_norm_h
 
@@ -72,7 +72,7 @@ class AdaptivePolicy:
 
     def switch_likely(self):
         """Will the norm of the cycle about to run change the precision?  Extrapolated from the last two norms of this
-        phase, as the engine does before it queues a speculative front part (csrc/mghip.hip, iterate_impl)."""
+        phase, as the engine does before it queues a speculative front part (csrc/mg_solve.hip, front_would_be_wasted)."""
         if self.floor_due():
             return True                # the floor is evaluated from the iterate the coming cycle leaves and usually ends the phase
         if self.promoted or self.phase != "f32" or len(self.hist) < 2:
@@ -102,7 +102,7 @@ class FixedPolicy:
 
 
 class DecomposedSolve:
-    """The loop of mg_iterate (csrc/mghip.hip; solvers/multigrid.py:219-246) on the decomposed hierarchy: policy check ->
+    """The loop of mg_iterate (csrc/mg_solve.hip; solvers/multigrid.py:219-246) on the decomposed hierarchy: policy check ->
     cycle -> ||r|| -> record -> absolute stop test, driving one DistributedMultigrid per working precision (they share the
     decomposition; the iterate moves between them with take_iterate_from, the on-device cast of
     PrecisionManager.convert_array).  bench.py --gpus N and DistributedMultigridSolver.solve both run THIS loop.
@@ -153,7 +153,7 @@ class DecomposedSolve:
             self.switches += 1
         sv = solvers[now]
         # no speculative front part across a precision switch the policy can see coming, nor across the end of the solve
-        # (it would run and be dropped): the norm in flight extrapolated from the last two, as iterate_impl does
+        # (it would run and be dropped): the norm in flight extrapolated from the last two, as front_would_be_wasted does
         ends = False
         if tol > 0.0 and len(policy.hist) >= 2 and policy.hist[-2] > 0:
             ends = policy.hist[-1] * min(1.0, policy.hist[-1] / policy.hist[-2]) < tol

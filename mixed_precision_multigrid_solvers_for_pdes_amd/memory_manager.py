@@ -3,7 +3,7 @@ dtype keyed free lists) and GPUMemoryManager (to_gpu / to_cpu, streams, statisti
 statistics keys, over torch device tensors instead of CuPy arrays.
 
 The solver itself does not allocate through a pool: `mg_create` allocates every level of the hierarchy once (one arena per
-handle, csrc/mghip.hip) and a solve allocates nothing.  These classes serve callers that stage their own device fields for
+handle, csrc/mg_engine.hip) and a solve allocates nothing.  These classes serve callers that stage their own device fields for
 the device-pointer entry points (`mg_dev_*`, include/mghip.h): 2-D allocations are PITCHED the way those entry points
 expect -- rows start on 512-byte boundaries (mg_pitch_elems) -- and handed out as the logical (nx, ny) view, so
 `t.stride(0)` is the `ld` argument and `t.data_ptr()` the field pointer."""

@@ -502,7 +502,7 @@ def var_coarse_residual(u, f, a, hx, hy, coeff, shift=0.0):
 class VarMGOracle(MGOracle):
     """MGOracle with A = coeff * div(a grad .): same cycle, variable-coefficient smoother / residual / coarsest solve.
     The coefficient of level l is every 2^l-th vertex value of the caller's array (re-discretisation), cast once to the
-    precision the level computes in (csrc/mghip.hip mg_set_coefficient does the same)."""
+    precision the level computes in (csrc/mg_engine.hip mg_set_coefficient does the same)."""
 
     def __init__(self, a, *args, **kw):
         super().__init__(a.shape[0], a.shape[1], *args, **kw)

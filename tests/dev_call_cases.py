@@ -18,7 +18,7 @@ ESIZE = {"f32": 4, "f64": 8}
 GUARD = 4                      # guard rows before and after every array of a call
 BIG = 1 << 30
 
-# ---- the kernels' own geometry (csrc/mg_kernels.hpp, csrc/mg_rb_kernels.hpp, csrc/mghip.hip) -----------------------------
+# ---- the kernels' own geometry (csrc/mg_kernels.hpp, csrc/mg_rb_kernels.hpp, csrc/mg_launch.hip) --------------------------
 K_TI = 32                      # kTI: tile rows of the single operators (jacobi / rbgs_colour / residual kernels, TileShape)
 TILE_ROW_BYTES = 512           # kTileRowBytes: TJ = 64 fp64 / 128 fp32 columns per LDS tile (TileShape, FusedShape)
 FUSED_TI = {"tiny": 8, "small": 16, "large": 32}     # kFusedTITiny / kFusedTISmall / kFusedTI

@@ -271,7 +271,7 @@ def test_precision_switch_between_two_decomposed_solvers():
 
 
 def test_adaptive_policy_host_port():
-    """distributed.AdaptivePolicy = csrc/mghip.hip adapt() (one-way rule): the trajectory of the 4097^2 bench problem
+    """distributed.AdaptivePolicy = csrc/mg_solve.hip adapt() (one-way rule): the trajectory of the 4097^2 bench problem
     (fp32 stagnates at its residual floor, the stagnation rule promotes after five cycles) and the threshold path."""
     p = D.AdaptivePolicy(1e-6)
     assert p.before_cycle(9.87) == "f32"                       # large first residual: single

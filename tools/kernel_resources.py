@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPR / LDS / occupancy of every kernel in libmghip (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
+"""VGPR / LDS / occupancy of every kernel of libmghip's kernel-launch unit (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
 
     python3 tools/kernel_resources.py [substring-of-mangled-name]
 """
@@ -9,7 +9,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "mixed_precision_multigrid_solvers_for_pdes_amd", "csrc", "mghip.hip")
+SRC = os.path.join(ROOT, "mixed_precision_multigrid_solvers_for_pdes_amd", "csrc", "mg_launch.hip")
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
        "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/_mg_res.so", SRC] + sys.argv[2:]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
