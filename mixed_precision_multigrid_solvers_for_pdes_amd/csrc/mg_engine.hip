@@ -954,6 +954,16 @@ int mg_time_op(mg_handle* h, int op, int level, int dtype, int reps, double* avg
   HIPC(&h->err, hipEventElapsedTime(&ms, e0, e1));
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   *avg_ms = (double)ms / reps;
+  // Outside the timed interval: leave the handle as a fresh one with this right-hand side and iterate would be.
+  // op 4 wrote the ring of the coarse rhs from lv[level].r, which the fused legs never write (they restrict into the interior
+  // only and rely on the rings injected once per right-hand side): inject the rings again, for either working precision.
+  if (op == 4) {
+    h->rings_gen[0] = h->rings_gen[1] = 0;
+    inject_rings_once(h, h->phase);
+  }
+  // ops 12 / 13: cycle_span marked `partials` as the sum r^2 of the current iterate, but lv[0].u is already the pre-smoothed
+  // iterate of the NEXT cycle (the solve loop drops the mark the same way once its front part is queued)
+  if (op == 12 || op == 13) h->norm_partials = 0;
   return rc;
 }
 

@@ -171,7 +171,7 @@ class HipOps:
         self._engine = MultigridEngine(NX, NY, domain, cfg["coeff"], cfg["levels"], cfg["cycle"], cfg["pre"], cfg["post"],
                                        cfg["smoother"], cfg["omega"], cfg["coarse_tol"], cfg["coarse_maxit"], prec,
                                        device=self.device.index or 0, mixed_split=max(split, 0))
-        _lib.check(self.lib.mg_set_stream(self._engine._h, self._stream(), 0))
+        self._engine.set_stream(self._stream())
 
     def coarse_coefficient(self, a_host):
         """vertex values of the diffusion coefficient on the agglomeration level (host array; None: constant)"""
@@ -183,11 +183,10 @@ class HipOps:
         rings of its coarser levels instead of injecting them again (mg_update_rhs_device)."""
         e = self._engine
         same_ring = bool(same_ring) and self._coarse_ring_valid
-        _lib.check(self.lib.mg_set_stream(e._h, self._stream(), 0))
-        fn = self.lib.mg_update_rhs_device if same_ring else self.lib.mg_set_rhs_device
-        _lib.check(fn(e._h, self._p(rhs_global), rhs_global.stride(0), self._code(rhs_global)))
+        e.set_stream(self._stream())
+        (e.update_rhs_device if same_ring else e.set_rhs_device)(rhs_global)
         self._coarse_ring_valid = True
-        _lib.check(self.lib.mg_zero_solution_device(e._h))
+        e.zero_solution_device()
         if self.rec is not None:
             self.rec.emit(_lib.MG_PLAN_COARSE_BEGIN, i=(rhs_global.stride(0), self._code(rhs_global), int(same_ring)), p=(e._h.value, rhs_global))
 
@@ -197,7 +196,7 @@ class HipOps:
             self.rec.emit(_lib.MG_PLAN_COARSE_CYCLE, i=(1,), p=(self._engine._h.value,))
 
     def coarse_end(self, out_global):
-        _lib.check(self.lib.mg_get_solution_device(self._engine._h, self._p(out_global), out_global.stride(0), self._code(out_global)))
+        self._engine.get_solution_device(out_global)
         if self.rec is not None:
             self.rec.emit(_lib.MG_PLAN_COARSE_END, i=(out_global.stride(0), self._code(out_global)), p=(self._engine._h.value, out_global))
 

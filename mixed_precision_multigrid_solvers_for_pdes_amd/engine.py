@@ -123,7 +123,8 @@ class MultigridEngine:
         return {"iterations": n, "converged": bool(conv.value), "residual_history": [hist[i] for i in range(n)],
                 "precision_codes": [prec[i] for i in range(n)], "initial_residual": stats.initial_residual,
                 "solve_seconds": stats.solve_seconds, "precision_switches": stats.precision_switches,
-                "switch_reason": _lib.SWITCH_REASONS.get(stats.switch_reason), "fp32_floor": stats.fp32_floor}
+                "switch_reason": _lib.SWITCH_REASONS.get(stats.switch_reason), "fp32_floor": stats.fp32_floor,
+                "last_coarse_sweeps": stats.last_coarse_sweeps}
 
     def set_coefficient(self, a):
         """Variable-coefficient operator A = coeff * div(a grad .): vertex values of a on the fine grid (None: back
@@ -176,6 +177,37 @@ class MultigridEngine:
 
     def synchronize(self):
         self._check(self._lib.mg_synchronize(self._h))
+
+    # ---- device-to-device forms (torch tensors): asynchronous on the handle's stream --------------
+    def _dev_args(self, t):
+        """(pointer, row pitch in elements, mg_dtype) of a 2-D device tensor (nx, ld) whose first ny columns are the field"""
+        return C.c_void_p(t.data_ptr()), int(t.stride(0)), _lib.dtype_code(str(t.dtype).split(".")[-1])
+
+    def set_rhs_device(self, t):
+        self._check(self._lib.mg_set_rhs_device(self._h, *self._dev_args(t)))
+
+    def update_rhs_device(self, t):
+        """a right-hand side whose boundary ring equals that of the last set_rhs / set_rhs_device (mg_update_rhs_device)"""
+        self._check(self._lib.mg_update_rhs_device(self._h, *self._dev_args(t)))
+
+    def zero_solution_device(self):
+        self._check(self._lib.mg_zero_solution_device(self._h))
+
+    def get_solution_device(self, t):
+        self._check(self._lib.mg_get_solution_device(self._h, *self._dev_args(t)))
+
+    def set_stream(self, stream):
+        """queue the handle's work on `stream` (a hipStream_t as an integer or c_void_p); None: back on the handle's own"""
+        if stream is None:
+            self._check(self._lib.mg_set_stream(self._h, None, 1))
+        else:
+            self._check(self._lib.mg_set_stream(self._h, stream if isinstance(stream, C.c_void_p) else C.c_void_p(int(stream)), 0))
+
+    def get_stream(self):
+        """the hipStream_t the handle's work is queued on, as an integer (0: the NULL stream)"""
+        out = C.c_void_p(None)
+        self._check(self._lib.mg_get_stream(self._h, C.byref(out)))
+        return out.value or 0
 
     def time_op(self, op, level=0, dtype=np.float64, reps=20):
         ops = {"jacobi": 0, "rbgs": 1, "residual": 2, "residual_norm": 3, "restrict": 4, "prolong": 5, "cycle": 6,
