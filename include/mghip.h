@@ -400,6 +400,66 @@ int mg_comm_destroy(void* comm);
 /* ranks of the communicator / this process's rank in it (what the bench line reports as ranks_seen) */
 int mg_comm_ranks(void* comm, int* nranks, int* rank);
 
+/* ------------------------------------------------------------------------------------------------
+ * Krylov outer loop: device-resident preconditioned conjugate gradients, M^-1 = num_cycles multigrid cycles from zero.
+ * No reference counterpart as a loop (preconditioning/multigrid_preconditioner.py:20-176 is the preconditioner alone, applied
+ * through host arrays).  An mg_pcg OWNS its preconditioner engine, built from `cfg`: cfg.precision must be MG_PREC_DOUBLE,
+ * MG_PREC_SINGLE_MANAGED or MG_PREC_MIXED_LEVELS, cfg.fmg_cycles 0 and cfg.coeff < 0 (an SPD operator); anything else returns
+ * MG_ERR_INVALID_VALUE before any device work.  The Krylov vectors are always fp64; only the preconditioner runs in
+ * cfg.precision.  flexible: 0 the Fletcher-Reeves beta = (r.z) / (r.z)_old, 1 the flexible (Polak-Ribiere) beta =
+ * -alpha (z.q) / (r.z)_old for a preconditioner that is not symmetric, < 0 auto: 1 exactly when cfg.smoother != MG_JACOBI or
+ * pre != post.  The reported norm is sqrt(hx hy (sum of r^2 over interior cells + sum of f^2 over the ring)), what
+ * mg_residual_norm gives for the same iterate; it is compared as norm < tol (absolute, like mg_iterate); hist[k] is the norm
+ * after iteration k + 1.  A breakdown (p.Ap <= 0 or non-finite) ends the solve with status 2 and converged = 0; it is not an
+ * error code, and the iterate returned is the last one before it.  All of the solver's work is queued on its engine's stream.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mg_pcg mg_pcg;
+typedef struct mg_pcg_stats {
+  double solve_seconds;      /* host wall time of the device-resident solve (initial residual ... true residual)          */
+  double precond_seconds;    /* device time of the preconditioner applications (events; beyond 128 iterations: their mean) */
+  double initial_residual;   /* ||f - A x0||                                                                               */
+  double true_residual;      /* ||f - A x|| of the returned iterate, recomputed by the residual-norm kernel                 */
+  int32_t iterations;
+  int32_t status;            /* 0 tolerance met, 1 max_iter, 2 breakdown (p.Ap <= 0 or non-finite)                         */
+} mg_pcg_stats;
+int mg_pcg_create(const mg_config* cfg, int num_cycles, int flexible, mg_pcg** out);
+int mg_pcg_destroy(mg_pcg* s);
+/* as mg_set_coefficient / mg_set_shift, for the outer operator and (forwarded) the engine's */
+int mg_pcg_set_coefficient(mg_pcg* s, const void* a_host_or_null, int host_dtype);
+int mg_pcg_set_shift(mg_pcg* s, double sigma);
+/* rhs, u0 (nullable: zero) and u_out are host arrays of host_dtype; the ring of u0 is the Dirichlet data */
+int mg_pcg_solve(mg_pcg* s, const void* rhs, const void* u0_or_null, void* u_out, int host_dtype, double tol, int max_iter,
+                 double* hist, int hist_cap, int* n_iter, int* converged, mg_pcg_stats* stats);
+/* device arrays of `dtype` with pitches in elements; x_dev -- in: initial guess + Dirichlet ring, out: the solution */
+int mg_pcg_solve_device(mg_pcg* s, const void* rhs_dev, int ld_rhs, void* x_dev, int ld_x, int dtype, double tol, int max_iter,
+                        double* hist, int hist_cap, int* n_iter, int* converged, mg_pcg_stats* stats);
+/* on (default): the preconditioner, dots, beta, direction and alpha of iteration k + 1 -- which write only z, p, q and scalars --
+ * are queued before the host waits for the norm of iteration k (dropped if that norm ends the solve).  Same bits either way. */
+int mg_pcg_set_lookahead(mg_pcg* s, int on);
+const char* mg_pcg_last_error(const mg_pcg* s);
+/* The field kernels of the loop, call by call: fp64 device arrays (nx, ny) with pitch `ld` (elements, even), 16-byte aligned;
+ * asynchronous on `stream` (nullable); scratch >= mg_dev_scratch_bytes(); scalars are doubles in device memory.  x carries the
+ * Dirichlet ring and only its interior cells change; the rings of r, p, q, z are zero and stay zero; sums run over interior
+ * cells, in a fixed order (same bits on every run).
+ *   direction: p_out = z + beta p_in (beta NULL: p_out = z, p_in is not read), q = A p_out with A = coeff (Laplacian_h - sigma)
+ *              or coeff (div(a grad .) - sigma) when `a` is given, *pq_dev = p_out . q.  Exactly the cells [0, nx) x [0, ny) of
+ *              p_out and q are stored (0 on the ring).  p_out is an array of its own: the kernel reads p_in across tile edges.
+ *   update:    x += alpha p, r -= alpha q on interior cells, *rr_dev = r . r; rows 1 .. nx - 2 are stored as whole 16-byte
+ *              vectors (ring and pad columns with the bits they held).  alpha == 0 stores nothing.
+ *   dots:      *rz_dev = r . z, and with q also *zq_dev = z . q, in one pass.
+ *   scalars:   the one-workgroup kernel between them -- reduces partials_a[0, na) (and partials_b[0, nb)) in fixed order and
+ *              advances a block of 10 doubles {rz, rz_old, zq, pq, alpha, beta, rr, flag, posted rr, posted flag}.  op 0: first dots
+ *              (rz; clears the flag), 1: dots, beta = rz / rz_old, 2: dots, beta = -alpha zq / rz_old, 3: direction, alpha = rz / pq
+ *              (pq <= 0 or non-finite: alpha = 0, flag = 1), 4: update, rr and the flag posted. */
+int mg_dev_pcg_direction(int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, const double* a_or_null,
+                         const double* z, const double* p_in_or_null, double* p_out, double* q, const double* beta_dev_or_null,
+                         void* scratch, double* pq_dev, void* stream);
+int mg_dev_pcg_update(int nx, int ny, int ld, const double* alpha_dev, const double* p, const double* q, double* x, double* r,
+                      void* scratch, double* rr_dev, void* stream);
+int mg_dev_pcg_dots(int nx, int ny, int ld, const double* r, const double* z, const double* q_or_null, void* scratch,
+                    double* rz_dev, double* zq_dev, void* stream);
+int mg_dev_pcg_scalars(int op, const double* partials_a, int na, const double* partials_b, int nb, double* scalars, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ from .facade import MixedPrecisionMultigrid, PoissonProblem, default_max_levels
 from . import applications, heat_equation
 from .heat_equation import HeatEquationConfig, HeatEquationSolver, TimeSteppingScheme
 from .applications import MultigridPreconditioner, PoissonSolver2D
+from .krylov import PCGEngine, PCGSolver
 
 __all__ = [
     "Grid", "BaseOperator", "LaplacianOperator", "DiffusionOperator", "HelmholtzOperator", "RestrictionOperator", "ProlongationOperator",
@@ -33,6 +34,6 @@ __all__ = [
     "SmoothingKernels", "TransferKernels", "MixedPrecisionKernels",
     "MixedPrecisionMultigrid", "PoissonProblem", "default_max_levels",
     "PoissonSolver2D", "MultigridPreconditioner", "applications", "heat_equation", "HeatEquationSolver",
-    "HeatEquationConfig", "TimeSteppingScheme",
+    "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver",
 ]
 __version__ = "0.1.0"

@@ -51,6 +51,13 @@ class MgStats(C.Structure):
     ]
 
 
+class MgPcgStats(C.Structure):
+    """mg_pcg_stats (include/mghip.h, "Krylov outer loop")"""
+    _fields_ = [("solve_seconds", C.c_double), ("precond_seconds", C.c_double), ("initial_residual", C.c_double),
+                ("true_residual", C.c_double), ("iterations", C.c_int32), ("status", C.c_int32)]
+
+
+PCG_STATUS = {0: "converged", 1: "max_iterations", 2: "breakdown"}
 SWITCH_REASONS = {0: None, 1: "threshold", 2: "stagnation", 3: "fp32_floor", 4: "fp32_skipped"}
 
 
@@ -140,6 +147,18 @@ SIGNATURES = {
     "mg_comm_unique_id": (_i, [C.c_char_p, _vp]),
     "mg_comm_init": (_i, [C.c_char_p, _vp, _i, _i, _i, C.POINTER(_vp)]),
     "mg_comm_destroy": (_i, [_vp]),
+    "mg_pcg_create": (_i, [C.POINTER(MgConfig), _i, _i, C.POINTER(_vp)]),
+    "mg_pcg_destroy": (_i, [_vp]),
+    "mg_pcg_set_coefficient": (_i, [_vp, _vp, _i]),
+    "mg_pcg_set_shift": (_i, [_vp, _d]),
+    "mg_pcg_solve": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _pd, _i, _pi, _pi, C.POINTER(MgPcgStats)]),
+    "mg_pcg_solve_device": (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _pd, _i, _pi, _pi, C.POINTER(MgPcgStats)]),
+    "mg_pcg_set_lookahead": (_i, [_vp, _i]),
+    "mg_pcg_last_error": (C.c_char_p, [_vp]),
+    "mg_dev_pcg_direction": (_i, [_i] * 3 + [_d] * 4 + [_vp] * 9),
+    "mg_dev_pcg_update": (_i, [_i] * 3 + [_vp] * 8),
+    "mg_dev_pcg_dots": (_i, [_i] * 3 + [_vp] * 7),
+    "mg_dev_pcg_scalars": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

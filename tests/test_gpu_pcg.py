@@ -1,0 +1,523 @@
+"""The device-resident conjugate-gradient loop (include/mghip.h "Krylov outer loop", csrc/mg_pcg.hip) on a GPU: its field
+kernels call by call against NumPy, whole solves against the restatement tests/pcg_reference.py (pinned on the CPU by
+tests/test_pcg_cpu.py), consistency between the ways of calling it, fp32 preconditioners, the problem the loop exists for,
+and the error contracts.
+
+Mixed-precision cases (part 4) -- what the restatement gives on the CPU with OraclePrecision-converted levels, V(2,2) Jacobi
+0.8, b = A x* for x* = default_rng(7).standard_normal with a zero ring, stop at 1e-10 ||b||:
+    129^2  -Laplacian     double / single_managed / mixed:  8 /  8 /  8 iterations, relative l-inf error 1.0e-10
+    129^2  checkerboard   double / single_managed / mixed: 22 / 22 / 22 iterations, relative l-inf error 4.8e-8
+    257^2  -Laplacian     double / single_managed / mixed:  8 /  8 /  8 iterations, relative l-inf error 9.7e-11
+    257^2  checkerboard   double / single_managed / mixed: 26 / 26 / 26 iterations, relative l-inf error 4.3e-8
+The restatement converged in every one of them, so none is dropped.  The test recomputes these and allows the device the
+restatement's count + 2 (fp32 rounding inside M perturbs the Krylov space) and 10 x its error."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import mixed_precision_multigrid_solvers_for_pdes_amd as mg
+from mixed_precision_multigrid_solvers_for_pdes_amd import _build, _lib
+from oracle import mg_oracle as O
+
+import pcg_reference as R
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 2            # NaN rows above and below every device field
+
+
+def _tile_shape():
+    """tile rows / fp64 tile columns of the direction kernel as built (csrc/mg_kernels.hpp)"""
+    text = open(os.path.join(_build.CSRC, "mg_kernels.hpp")).read()
+    ti = int(re.search(r"constexpr int kTI = (\d+);", text).group(1))
+    row_bytes = int(re.search(r"constexpr int kTileRowBytes = (\d+);", text).group(1))
+    return ti, row_bytes // 8
+
+
+TI, TJ = _tile_shape()
+SHAPES = [(5, 5), (9, 17), (67, 131), (129, 257), (33, 2049),
+          (TI - 1, TJ - 1), (TI, TJ), (TI + 1, TJ + 1), (2 * TI - 1, 2 * TJ - 1), (2 * TI, 2 * TJ), (2 * TI + 1, 2 * TJ + 1)]
+DYADIC = (2.0 ** -5, 2.0 ** -6)
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _pitches(ny):
+    ld = C.c_int(0)
+    _lib.check(_lib.load().mg_pitch_elems(_lib.MG_F64, ny, C.byref(ld)))
+    return [ld.value, (ny + 1) // 2 * 2]
+
+
+class Field:
+    """an (nx, ny) fp64 device field with pitch ld between NaN guard rows; pad columns start as NaN too"""
+
+    def __init__(self, arr, ld, fill=None):
+        torch = _torch()
+        nx, ny = arr.shape
+        host = np.full((nx + 2 * GUARD, ld), np.nan)
+        host[GUARD:GUARD + nx, :ny] = arr if fill is None else fill
+        self.nx, self.ny, self.ld = nx, ny, ld
+        self.t = torch.from_numpy(host).cuda()
+        self.start = host.copy()
+        self.ptr = C.c_void_p(self.t[GUARD:].data_ptr())
+
+    def numpy(self):
+        return self.t.cpu().numpy()
+
+    def field(self):
+        return self.numpy()[GUARD:GUARD + self.nx, :self.ny]
+
+    def outside_untouched(self, rows=None):
+        """guards and pad columns (and, with rows = (lo, hi), every row of the field outside [lo, hi)) still hold their bits"""
+        now, start = self.numpy().view(np.uint64), self.start.view(np.uint64)
+        mask = np.ones(now.shape, dtype=bool)
+        lo, hi = (0, self.nx) if rows is None else rows
+        mask[GUARD + lo:GUARD + hi, :self.ny] = False
+        return bool(np.all(now[mask] == start[mask]))
+
+
+def _scalar(value=np.nan):
+    return _torch().tensor([value], dtype=_torch().float64, device="cuda")
+
+
+def _scratch(nx, ny):
+    n = C.c_int64(0)
+    _lib.check(_lib.load().mg_dev_scratch_bytes(nx, ny, C.byref(n)))
+    return _torch().full((n.value // 8,), float("nan"), dtype=_torch().float64, device="cuda")
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a) + 0.0, np.ascontiguousarray(b) + 0.0          # -0 -> +0: the sign of a zero is not pinned
+    return bool(np.all(a.view(np.uint64) == b.view(np.uint64)))
+
+
+def _fields(nx, ny, seed):
+    rng = np.random.default_rng(seed)
+    z, p, x = (rng.standard_normal((nx, ny)) for _ in range(3))
+    a = 1.0 + 0.5 * rng.random((nx, ny)) + 50.0 * (rng.random((nx, ny)) > 0.7)
+    return R.zero_ring(z), R.zero_ring(p), x, a
+
+
+def _np_operator(p, hx, hy, sigma, a):
+    if a is None:
+        return O.apply_laplacian(p, hx, hy, -1.0, sigma)
+    return R.zero_ring(-O.var_residual(p, np.zeros_like(p), a, hx, hy, -1.0, sigma))
+
+
+def _direction(nx, ny, ld, hx, hy, sigma, a, z, p, beta, p_fill=None):
+    lib = _lib.load()
+    fz, fq, fpo = Field(z, ld), Field(z, ld, fill=np.nan), Field(z, ld, fill=np.nan)
+    fp = Field(p, ld, fill=p_fill)
+    fa = Field(a, ld) if a is not None else None
+    pq, scratch = _scalar(), _scratch(nx, ny)
+    bdev = None if beta is None else _scalar(beta)
+    _lib.check(lib.mg_dev_pcg_direction(nx, ny, ld, hx, hy, -1.0, sigma, fa.ptr if fa else None, fz.ptr, fp.ptr, fpo.ptr, fq.ptr,
+                                        None if bdev is None else _p(bdev), _p(scratch), _p(pq), None))
+    _torch().cuda.synchronize()
+    for f in (fz, fp) + ((fa,) if fa else ()):
+        assert f.outside_untouched(rows=(0, 0)), "an input of the direction kernel was written"
+    assert fpo.outside_untouched() and fq.outside_untouched(), "the direction kernel stored outside [0, nx) x [0, ny)"
+    return fpo.field(), fq.field(), float(pq.cpu()[0])
+
+
+# ------------------------------------------------------------------------------------------ 1. kernels, call by call
+@pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def test_direction_kernel(shape):
+    nx, ny = shape
+    z, p, _, a = _fields(nx, ny, nx * 7 + ny)
+    hx, hy = DYADIC
+    for ld in _pitches(ny):
+        for coef in (None, a):
+            for sigma in (0.0, 0.37):
+                for beta in (None, 0.0, -0.625, 1.7):
+                    want_p = z.copy() if beta is None else R.zero_ring(z + beta * p)
+                    want_q = _np_operator(want_p, hx, hy, sigma, coef)
+                    got_p, got_q, pq = _direction(nx, ny, ld, hx, hy, sigma, coef, z, p, beta)
+                    what = "%dx%d ld %d var %s sigma %g beta %r" % (nx, ny, ld, coef is not None, sigma, beta)
+                    assert _same_bits(got_p, want_p), "p: " + what
+                    assert _same_bits(got_q, want_q), "q: " + what
+                    assert not got_p[0].any() and not got_p[-1].any() and not got_p[:, 0].any() and not got_p[:, -1].any()
+                    assert not got_q[0].any() and not got_q[-1].any() and not got_q[:, 0].any() and not got_q[:, -1].any()
+                    ref = math.fsum((want_p * want_q).ravel().tolist())
+                    assert abs(pq - ref) <= 1e-13 * abs(ref), "p.q: %s: %r vs %r" % (what, pq, ref)
+    # beta NULL: p is not read -- the same bits with NaN in it
+    ld = _pitches(ny)[0]
+    got_p, got_q, pq = _direction(nx, ny, ld, hx, hy, 0.0, None, z, p, None, p_fill=np.nan)
+    ref_p, ref_q, ref_pq = _direction(nx, ny, ld, hx, hy, 0.0, None, z, p, 0.0)
+    assert _same_bits(got_p, ref_p) and _same_bits(got_q, ref_q) and pq == ref_pq
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def test_direction_kernel_non_dyadic_and_residual_kernel(shape):
+    nx, ny = shape
+    z, p, _, a = _fields(nx, ny, nx + 3 * ny)
+    lib = _lib.load()
+    ld = _pitches(ny)[0]
+    # q == -(mg_dev_residual(p, f = 0)) bit for bit (the residual kernels' own operator expression)
+    hx, hy = DYADIC
+    got_p, got_q, _ = _direction(nx, ny, ld, hx, hy, 0.0, None, z, p, 0.5)
+    fp, ff, fr = Field(got_p, ld), Field(np.zeros((nx, ny)), ld), Field(got_p, ld, fill=np.nan)
+    _lib.check(lib.mg_dev_residual(_lib.MG_F64, nx, ny, ld, hx, hy, -1.0, fp.ptr, ff.ptr, fr.ptr, None))
+    _torch().cuda.synchronize()
+    assert _same_bits(got_q, -fr.field())
+    # a non-dyadic domain: 1 / h^2 is rounded, the kernel multiplies where NumPy divides: p stays exact, q within 4 ulp of the
+    # largest term of the stencil sum, diag * max |p|
+    hx, hy = 1.3 / (nx - 1), 0.7 / (ny - 1)
+    for coef in (None, a):
+        for sigma in (0.0, 0.37):
+            got_p, got_q, pq = _direction(nx, ny, ld, hx, hy, sigma, coef, z, p, -0.625)
+            want_p = R.zero_ring(z + -0.625 * p)
+            want_q = _np_operator(want_p, hx, hy, sigma, coef)
+            assert _same_bits(got_p, want_p)
+            amax = 1.0 if coef is None else float(np.max(coef))
+            bound = 4 * np.finfo(np.float64).eps * amax * (2 / hx**2 + 2 / hy**2 + sigma) * float(np.max(np.abs(want_p)))
+            assert float(np.max(np.abs(got_q - want_q))) <= bound
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def test_update_and_dots_kernels(shape):
+    nx, ny = shape
+    lib = _lib.load()
+    rng = np.random.default_rng(nx * 11 + ny)
+    p, q, r = (R.zero_ring(rng.standard_normal((nx, ny))) for _ in range(3))
+    x = rng.standard_normal((nx, ny))                    # its ring is Dirichlet data
+    z = R.zero_ring((0.5 + rng.random((nx, ny))) * r + 0.1 * rng.standard_normal((nx, ny)))   # r.z > 0, like M r
+    qq = R.zero_ring((0.5 + rng.random((nx, ny))) * z + 0.1 * rng.standard_normal((nx, ny)))
+    for ld in _pitches(ny):
+        for alpha in (0.4375, -1.0 / 3.0):
+            fp, fq, fx, fr = Field(p, ld), Field(q, ld), Field(x, ld), Field(r, ld)
+            rr, scratch, adev = _scalar(), _scratch(nx, ny), _scalar(alpha)
+            _lib.check(lib.mg_dev_pcg_update(nx, ny, ld, _p(adev), fp.ptr, fq.ptr, fx.ptr, fr.ptr, _p(scratch), _p(rr), None))
+            _torch().cuda.synchronize()
+            want_x, want_r = x.copy(), r.copy()
+            want_x[1:-1, 1:-1] = x[1:-1, 1:-1] + alpha * p[1:-1, 1:-1]
+            want_r[1:-1, 1:-1] = r[1:-1, 1:-1] - alpha * q[1:-1, 1:-1]
+            assert _same_bits(fx.field(), want_x) and _same_bits(fr.field(), want_r)
+            for f in (fp, fq):
+                assert f.outside_untouched(rows=(0, 0))
+            assert fx.outside_untouched() and fr.outside_untouched()
+            ref = math.fsum((want_r[1:-1, 1:-1] ** 2).ravel().tolist())
+            assert abs(float(rr.cpu()[0]) - ref) <= 1e-13 * ref
+        for with_q in (False, True):
+            fr, fz, fq = Field(r, ld), Field(z, ld), Field(qq, ld)
+            rz, zq, scratch = _scalar(), _scalar(), _scratch(nx, ny)
+            _lib.check(lib.mg_dev_pcg_dots(nx, ny, ld, fr.ptr, fz.ptr, fq.ptr if with_q else None, _p(scratch), _p(rz), _p(zq), None))
+            _torch().cuda.synchronize()
+            for f in (fr, fz, fq):
+                assert f.outside_untouched(rows=(0, 0))
+            ref = math.fsum((r * z).ravel().tolist())
+            assert abs(float(rz.cpu()[0]) - ref) <= 1e-13 * abs(ref)
+            if with_q:
+                ref = math.fsum((z * qq).ravel().tolist())
+                assert abs(float(zq.cpu()[0]) - ref) <= 1e-13 * abs(ref)
+            else:
+                assert math.isnan(float(zq.cpu()[0]))
+
+
+def test_scalars_kernel_and_breakdown():
+    """the one-workgroup kernel between the field kernels: beta, alpha and the breakdown flag (p.Ap <= 0 or non-finite)"""
+    lib = _lib.load()
+    torch = _torch()
+    RZ, RZ_OLD, ZQ, PQ, ALPHA, BETA, RR, FLAG = range(8)
+
+    def step(op, sc, pa, pb=None):
+        ta = torch.tensor(pa, dtype=torch.float64, device="cuda")
+        tb = None if pb is None else torch.tensor(pb, dtype=torch.float64, device="cuda")
+        _lib.check(lib.mg_dev_pcg_scalars(op, _p(ta), len(pa), None if tb is None else _p(tb), 0 if pb is None else len(pb), _p(sc), None))
+        torch.cuda.synchronize()
+        return sc.cpu().numpy()
+
+    sc = torch.full((10,), 7.0, dtype=torch.float64, device="cuda")
+    s = step(0, sc, [1.0, 2.0, 3.0])
+    assert s[RZ] == 6.0 and s[FLAG] == 0.0
+    s = step(3, sc, [0.5] * 3000)                      # more partials than threads
+    assert s[PQ] == 1500.0 and s[ALPHA] == 6.0 / 1500.0 and s[FLAG] == 0.0
+    s = step(1, sc, [3.0])
+    assert s[RZ] == 3.0 and s[RZ_OLD] == 6.0 and s[BETA] == 0.5
+    s = step(2, sc, [4.0], [2.0, 1.0])
+    assert s[RZ] == 4.0 and s[ZQ] == 3.0 and s[BETA] == -(6.0 / 1500.0) * 3.0 / 3.0
+    s = step(4, sc, [9.0, 16.0])
+    assert s[RR] == 25.0 and s[8] == 25.0 and s[9] == 0.0
+    for bad in ([0.0], [-1.0, 0.5], [float("inf")], [float("nan")]):
+        step(0, sc, [1.0])
+        s = step(3, sc, bad)
+        assert s[FLAG] == 1.0 and s[ALPHA] == 0.0, bad
+        s = step(4, sc, [1.0])
+        assert s[9] == 1.0
+
+
+# ------------------------------------------------------------------------------------------ 2. whole solves
+def _smoother(name, omega):
+    return mg.JacobiSmoother(relaxation_parameter=omega) if name == "jacobi" else mg.GaussSeidelSmoother(red_black=True, relaxation_parameter=omega)
+
+
+def _operator(a, shift=0.0):
+    if a is not None:
+        return mg.DiffusionOperator(a)
+    return mg.HelmholtzOperator(shift) if shift else mg.LaplacianOperator(coefficient=-1.0)
+
+
+def _coefficient(kind, nx, ny):
+    return {None: None, "checker": R.checkerboard(nx, ny), "smooth": R.smooth_coefficient(nx, ny)}[kind]
+
+
+def _rel_tol(mgo, b, rel=1e-10):
+    hx, hy = mgo.h[0]
+    return rel * float(np.sqrt(hx * hy * np.sum(b * b)))
+
+
+def _solver(nx, ny, a, pre, post, sm, om, tol, flexible=None, precision="double", max_iterations=60, lookahead=None):
+    s = mg.PCGSolver(max_levels=R.full_levels(nx, ny), max_iterations=max_iterations, tolerance=tol, cycle_type="V",
+                     pre_smooth_iterations=pre, post_smooth_iterations=post, flexible=flexible, precision=precision)
+    s.setup(mg.Grid(nx, ny), _operator(a), smoother=_smoother(sm, om))
+    if lookahead is not None:
+        s._engine.set_lookahead(lookahead)
+    return s
+
+
+SOLVES = [("laplace_v11_65", 65, 65, None, 1, 1, "jacobi", 0.8),
+          ("laplace_v22_65", 65, 65, None, 2, 2, "jacobi", 0.8),
+          ("checker_v22_65", 65, 65, "checker", 2, 2, "jacobi", 0.8),
+          ("smooth_rbgs_v11_65", 65, 65, "smooth", 1, 1, "rbgs", 1.0),
+          ("laplace_v11_129x65", 129, 65, None, 1, 1, "jacobi", 0.8),
+          ("checker_v22_129", 129, 129, "checker", 2, 2, "jacobi", 0.8)]
+
+
+@pytest.mark.parametrize("case", SOLVES, ids=[c[0] for c in SOLVES])
+def test_solve_equals_restatement(case):
+    _, nx, ny, kind, pre, post, sm, om = case
+    a = _coefficient(kind, nx, ny)
+    mgo = R.make_oracle(nx, ny, a, pre, post, sm, om)
+    b = R.random_rhs(nx, ny)
+    tol = _rel_tol(mgo, b)
+    flex = R.default_flexible(sm, pre, post)
+    want, winfo = R.pcg(mgo, b, tol=tol, max_iterations=60, flexible=flex)
+    s = _solver(nx, ny, a, pre, post, sm, om, tol)
+    got, info = s.solve(s.grid, s.operator, b)
+    s.close()
+    print(case[0], "iterations", info["iterations"], winfo["iterations"], "true", info["true_residual"], "last", info["final_residual"])
+    assert winfo["converged"] and info["converged"] and info["status"] == "converged" and info["flexible"] == flex
+    assert info["iterations"] == winfo["iterations"]
+    np.testing.assert_allclose(info["residual_history"], winfo["residual_history"], rtol=1e-10, atol=0)
+    assert float(np.max(np.abs(got - want))) <= 1e-12 * float(np.max(np.abs(want)))
+    assert abs(info["true_residual"] - info["final_residual"]) <= 1e-2 * info["final_residual"]
+    np.testing.assert_allclose(info["initial_residual"], winfo["initial_residual"], rtol=1e-12)
+
+
+# ------------------------------------------------------------------------------------------ 3. consistency
+def test_ring_term_and_dirichlet_ring():
+    n = 65
+    rng = np.random.default_rng(5)
+    f = rng.standard_normal((n, n))                     # non-zero ring: a floor under the norm, so stop by count
+    u0 = np.zeros((n, n)); u0[0, :] = 1.0; u0[:, -1] = np.linspace(1, 2, n); u0[-1, :] = -0.5
+    mgo = R.make_oracle(n, n, None, 2, 2)
+    want, winfo = R.pcg(mgo, f, u0=u0, tol=1e-30, max_iterations=6)
+    s = _solver(n, n, None, 2, 2, "jacobi", 0.8, 1e-30, max_iterations=6)
+    got, info = s.solve(s.grid, s.operator, f, initial_guess=u0)
+    s.close()
+    assert winfo["iterations"] == 6 and info["iterations"] == 6 and not info["converged"] and info["status"] == "max_iterations"
+    for sl in ((0, slice(None)), (-1, slice(None)), (slice(None), 0), (slice(None), -1)):
+        np.testing.assert_array_equal(got[sl], u0[sl])
+    assert float(np.max(np.abs(got - want))) <= 1e-12 * float(np.max(np.abs(want)))
+    assert abs(info["final_residual"] - mgo.residual_norm(got, f)) <= 1e-12 * info["final_residual"]
+    assert abs(info["true_residual"] - mgo.residual_norm(got, f)) <= 1e-12 * info["true_residual"]
+
+
+def test_lookahead_repeated_solves_and_operator_changes_give_the_same_bits():
+    n = 65
+    a = R.checkerboard(n, n)
+    b1, b2 = R.random_rhs(n, n, 1), R.random_rhs(n, n, 2)
+    mgo = R.make_oracle(n, n, a, 2, 2)
+    tol = _rel_tol(mgo, b1)
+
+    def run(lookahead, rhs, solver=None):
+        s = solver or _solver(n, n, a, 2, 2, "jacobi", 0.8, tol, lookahead=lookahead)
+        u, info = s.solve(s.grid, s.operator, rhs)
+        return s, u, info
+
+    s_on, u_on, i_on = run(True, b1)
+    s_off, u_off, i_off = run(False, b1)
+    assert _same_bits(u_on, u_off) and i_on["residual_history"] == i_off["residual_history"] and i_on["iterations"] == i_off["iterations"]
+    assert i_on["true_residual"] == i_off["true_residual"]
+    # a second solve on the same solver == a fresh solver
+    _, u2, i2 = run(True, b2, s_on)
+    s_new, u2n, i2n = run(True, b2)
+    assert _same_bits(u2, u2n) and i2["residual_history"] == i2n["residual_history"]
+    # the same right-hand side again: the same bits as the first time
+    _, u1b, i1b = run(True, b1, s_on)
+    assert _same_bits(u1b, u_on) and i1b["residual_history"] == i_on["residual_history"]
+    for s in (s_off, s_new):
+        s.close()
+    # set_coefficient / set_shift on a used solver == a fresh solver built with them
+    a2 = R.smooth_coefficient(n, n)
+    s_on._engine.set_coefficient(a2)
+    op = mg.HelmholtzOperator(0.37)                     # solve() forwards its shift
+    u3, i3 = s_on.solve(s_on.grid, op, b1)
+    fresh = mg.PCGSolver(max_levels=R.full_levels(n, n), max_iterations=60, tolerance=tol, pre_smooth_iterations=2, post_smooth_iterations=2)
+    fresh.setup(mg.Grid(n, n), mg.DiffusionOperator(a2), smoother=_smoother("jacobi", 0.8))
+    u3n, i3n = fresh.solve(fresh.grid, op, b1)
+    assert i3["converged"] and _same_bits(u3, u3n) and i3["residual_history"] == i3n["residual_history"]
+    want, winfo = R.pcg(R.make_oracle(n, n, a2, 2, 2, shift=0.37), b1, tol=tol, max_iterations=60)
+    assert i3["iterations"] == winfo["iterations"]
+    assert float(np.max(np.abs(u3 - want))) <= 1e-12 * float(np.max(np.abs(want)))
+    s_on._engine.set_coefficient(None)                  # and back to constant coefficients, shift 0
+    u4, i4 = s_on.solve(s_on.grid, mg.LaplacianOperator(), b1)
+    want, winfo = R.pcg(R.make_oracle(n, n, None, 2, 2), b1, tol=tol, max_iterations=60)
+    assert i4["iterations"] == winfo["iterations"] and float(np.max(np.abs(u4 - want))) <= 1e-12 * float(np.max(np.abs(want)))
+    s_on.close(); fresh.close()
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+def test_host_solve_equals_device_solve(dt):
+    torch = _torch()
+    n = 65
+    b = R.random_rhs(n, n, 4).astype(dt)
+    u0 = np.zeros((n, n), dtype=dt); u0[0, :] = 1.0
+    mgo = R.make_oracle(n, n, None, 1, 1)
+    tol = _rel_tol(mgo, b.astype(np.float64), 1e-6 if dt == np.float32 else 1e-10)
+    s = _solver(n, n, None, 1, 1, "jacobi", 0.8, tol)
+    got, info = s.solve(s.grid, s.operator, b, initial_guess=u0)
+    assert got.dtype == dt and info["converged"]
+    ld = n + 3 if dt == np.float32 else n + 5           # a caller's pitch, not the library's
+    rhs_t = torch.full((n, ld), float("nan"), dtype=getattr(torch, np.dtype(dt).name), device="cuda")
+    x_t = rhs_t.clone()
+    rhs_t[:, :n] = torch.from_numpy(b).cuda()
+    x_t[:, :n] = torch.from_numpy(u0).cuda()
+    dinfo = s._engine.solve_device(rhs_t, x_t, tol, 60)
+    torch.cuda.synchronize()
+    s.close()
+    assert _same_bits(x_t[:, :n].cpu().numpy().astype(np.float64), got.astype(np.float64))
+    assert bool(torch.isnan(x_t[:, n:]).all()) and bool(torch.isnan(rhs_t[:, n:]).all())
+    assert dinfo["residual_history"] == info["residual_history"] and dinfo["iterations"] == info["iterations"]
+
+
+# ------------------------------------------------------------------------------------------ 4. fp32 preconditioners
+_MIXED_REF = {}
+
+
+def _mixed_reference(n, kind, prec):
+    """(x*, b, tol, restatement's count, restatement's error), computed once per case"""
+    key = (n, kind, prec)
+    if key not in _MIXED_REF:
+        a = _coefficient(kind, n, n)
+        mgo = R.make_oracle(n, n, a, 2, 2)
+        xs = R.zero_ring(np.random.default_rng(7).standard_normal((n, n)))
+        b = R.apply_A(mgo, xs)
+        tol = _rel_tol(mgo, b)
+        x, info = R.pcg(mgo, b, tol=tol, max_iterations=80, pm=R.precision_manager(prec))
+        assert info["converged"], "the restatement does not converge for %r" % (key,)
+        _MIXED_REF[key] = (xs, b, tol, info["iterations"], float(np.max(np.abs(x - xs)) / np.max(np.abs(xs))))
+    return _MIXED_REF[key]
+
+
+@pytest.mark.parametrize("prec", ["single_managed", "mixed"])
+@pytest.mark.parametrize("kind", [None, "checker"], ids=["laplace", "checker"])
+@pytest.mark.parametrize("n", [129, 257])
+def test_fp32_preconditioner(n, kind, prec):
+    xs, b, tol, count, err = _mixed_reference(n, kind, prec)
+    s = _solver(n, n, _coefficient(kind, n, n), 2, 2, "jacobi", 0.8, tol, precision=prec, max_iterations=80)
+    got, info = s.solve(s.grid, s.operator, b)
+    s.close()
+    gerr = float(np.max(np.abs(got - xs)) / np.max(np.abs(xs)))
+    print(n, kind, prec, "iterations", info["iterations"], "restatement", count, "error", gerr, "restatement", err,
+          "true / tol", info["true_residual"] / tol)
+    assert info["converged"] and info["final_residual"] < tol
+    assert info["iterations"] <= count + 2
+    assert info["true_residual"] < 2 * tol
+    assert gerr <= 10 * err
+
+
+# ------------------------------------------------------------------------------------------ 5. the point of the feature
+def test_checkerboard_where_plain_multigrid_stalls():
+    n = 129
+    a = R.checkerboard(n, n)
+    b = R.random_rhs(n, n)
+    mgo = R.make_oracle(n, n, a, 2, 2)
+    tol = _rel_tol(mgo, b)
+    cycles, last = R.plain_multigrid(mgo, b, tol, 60)
+    assert cycles is None and last > tol, "the plain cycle met 1e-10 ||b|| within 60 cycles on the oracle"
+    ms = mg.MultigridSolver(max_levels=R.full_levels(n, n), max_iterations=60, tolerance=tol)
+    ms.setup(mg.Grid(n, n), mg.DiffusionOperator(a), mg.RestrictionOperator("full_weighting"), mg.ProlongationOperator("bilinear"),
+             smoother=_smoother("jacobi", 0.8))
+    _, minfo = ms.solve(ms.grids[0], mg.DiffusionOperator(a), b)
+    assert not minfo["converged"]
+    want, winfo = R.pcg(R.make_oracle(n, n, a, 2, 2), b, tol=tol, max_iterations=60)
+    s = _solver(n, n, a, 2, 2, "jacobi", 0.8, tol)
+    got, info = s.solve(s.grid, s.operator, b)
+    s.close()
+    assert info["converged"] and info["iterations"] == winfo["iterations"] == 28
+
+
+# ------------------------------------------------------------------------------------------ 6. error contracts
+def _config(**kw):
+    base = dict(nx=33, ny=33, x0=0.0, x1=1.0, y0=0.0, y1=1.0, coeff=-1.0, max_levels=4, cycle=0, pre=1, post=1, smoother=0,
+                omega=0.8, coarse_tol=1e-12, coarse_maxit=1000, precision=_lib.MG_PREC_DOUBLE, switch_threshold=1e-6,
+                memory_threshold_gb=4.0, adaptive_reference_rule=0, device=0, profile=0, colour_offset=0, fused=2, tail=1,
+                fmg_cycles=0, speculate=2, coarse_direct=0, mixed_split=0)
+    base.update(kw)
+    return _lib.MgConfig(**base)
+
+
+def test_error_contracts():
+    lib = _lib.load()
+    for bad in (dict(precision=_lib.MG_PREC_ADAPTIVE), dict(precision=_lib.MG_PREC_DEFECT), dict(precision=_lib.MG_PREC_SINGLE),
+                dict(fmg_cycles=1), dict(coeff=1.0), dict(coeff=0.0)):
+        h = C.c_void_p(None)
+        cfg = _config(**bad)
+        assert lib.mg_pcg_create(C.byref(cfg), 1, -1, C.byref(h)) == _lib.MG_ERR_INVALID_VALUE, bad
+        assert not h.value and lib.mg_pcg_last_error(None)
+    h, cfg = C.c_void_p(None), _config()
+    assert lib.mg_pcg_create(C.byref(cfg), 0, -1, C.byref(h)) == _lib.MG_ERR_INVALID_VALUE and not h.value
+    assert lib.mg_pcg_create(C.byref(cfg), 1, -1, C.byref(h)) == _lib.MG_OK and h.value
+    n = 33
+    b = R.random_rhs(n, n)
+    out = np.full((n, n), 7.0)
+    hist = (C.c_double * 4)(*([-1.0] * 4))
+    nit, conv, stats = C.c_int(-5), C.c_int(-5), _lib.MgPcgStats()
+    stats.iterations = -5
+
+    def untouched():
+        return bool(np.all(out == 7.0)) and list(hist) == [-1.0] * 4 and nit.value == -5 and conv.value == -5 and stats.iterations == -5
+
+    args = lambda **kw: [kw.get("h", h), kw.get("rhs", _lib.ptr(b)), None, kw.get("out", _lib.ptr(out)), kw.get("dt", _lib.MG_F64), 1e-8,
+                         kw.get("max_iter", 4), kw.get("hist", hist), kw.get("cap", 4), kw.get("nit", C.byref(nit)),
+                         kw.get("conv", C.byref(conv)), C.byref(stats)]
+    for bad in (dict(cap=0), dict(hist=None), dict(nit=None), dict(conv=None), dict(rhs=None), dict(out=None), dict(dt=5),
+                dict(max_iter=0), dict(h=None)):
+        assert lib.mg_pcg_solve(*args(**bad)) == _lib.MG_ERR_INVALID_VALUE, bad
+        assert untouched(), bad
+    # the device form: a pitch below ny is a shape mismatch
+    torch = _torch()
+    t = torch.zeros((n, n + 1), dtype=torch.float64, device="cuda")
+    assert lib.mg_pcg_solve_device(h, _p(t), n - 1, _p(t), n + 1, _lib.MG_F64, 1e-8, 4, hist, 4, C.byref(nit), C.byref(conv),
+                                   C.byref(stats)) == _lib.MG_ERR_INVALID_VALUE
+    assert untouched() and b"pitch" in lib.mg_pcg_last_error(h)
+    assert lib.mg_pcg_set_shift(h, -1.0) == _lib.MG_ERR_INVALID_VALUE
+    assert lib.mg_pcg_set_coefficient(h, None, 7) == _lib.MG_ERR_INVALID_VALUE
+    # max_iter reached: status 1, and the solver is still usable
+    assert lib.mg_pcg_solve(*args(max_iter=2)) == _lib.MG_OK
+    assert nit.value == 2 and conv.value == 0 and stats.status == 1 and stats.iterations == 2 and hist[1] > 0 and hist[2] == -1.0
+    assert np.all(np.isfinite(out))
+    assert lib.mg_pcg_destroy(h) == _lib.MG_OK
+    # the Python layer: shapes are checked before the call
+    s = _solver(33, 33, None, 1, 1, "jacobi", 0.8, 1e-8)
+    with pytest.raises(ValueError, match="grid mismatch"):
+        s.solve(mg.Grid(17, 17), s.operator, np.zeros((17, 17)))
+    with pytest.raises(ValueError, match="grid mismatch"):
+        s._engine.solve(np.zeros((33, 17)))
+    with pytest.raises(ValueError, match="initial guess"):
+        s._engine.solve(np.zeros((33, 33)), u0=np.zeros((17, 17)))
+    with pytest.raises(ValueError, match="coefficient shape"):
+        s._engine.set_coefficient(np.ones((17, 17)))
+    s.close()
