@@ -460,6 +460,66 @@ int mg_dev_pcg_dots(int nx, int ny, int ld, const double* r, const double* z, co
                     double* rz_dev, double* zq_dev, void* stream);
 int mg_dev_pcg_scalars(int op, const double* partials_a, int na, const double* partials_b, int nb, double* scalars, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Time stepping: device-resident steps of the heat equation  du/dt = alpha Laplace(u) + g(t) S(x, y)  with Dirichlet data.
+ * Replaces the step bodies of applications/heat_equation.py:155-266 (explicit / implicit Euler, Crank-Nicolson; the
+ * reference only names BDF2, :30) and the transfers around them: the state never leaves the device between steps.
+ * An mg_heat OWNS its inner solver, an engine built from `cfg`: cfg.precision must be MG_PREC_DOUBLE, cfg.coeff -1 and
+ * cfg.fmg_cycles 0; anything else (or alpha <= 0) returns MG_ERR_INVALID_VALUE before any device work.  It holds four fp64
+ * state slots (0..3), one right-hand-side buffer and an optional source profile S, all in the library's pitch; all of its
+ * work is queued on the engine's stream.
+ *
+ * mg_heat_step is functional on slots: it reads `src` (and `prev`, the level before it, for BDF2; -1 otherwise) and writes
+ * `dst`, which differs from both.  g0 = g(t), g1 = g(t + dt) are the time factors of the source; edge4 = {left (i = 0),
+ * right (i = nx - 1), bottom (j = 0), top (j = ny - 1)} are the uniform Dirichlet values at t + dt, applied in that order
+ * (corners carry bottom / top); edge4 == NULL keeps the ring of `src` (time-independent data of any shape).
+ *   implicit schemes: f and sum f^2 in one kernel -> engine right-hand side -> shift lambda (1/(dt a), 2/(dt a), 3/(2 dt a))
+ *     -> initial guess -> cycles until ||r|| < tol * max(1, ||f||_h) or max_cycles -> dst.  With bc_before_solve = 0 (the
+ *     reference's order, :209-225) the solve starts from `src` as it is -- it carries the boundary data of the OLD time
+ *     level -- and the ring of dst is set from edge4 afterwards; with 1 the guess is `src` with the ring from edge4, so the
+ *     solve sees the boundary data of t + dt.
+ *   explicit Euler: one kernel from src to dst, then the ring from edge4 if given; info is zero but for converged = 1.
+ *   BDF2 is (3 u_new - 4 u + u_prev) / (2 dt) = alpha Laplace(u_new) + g1 S; the caller starts it (one Crank-Nicolson step).
+ * mg_heat_diff_norm: sqrt of the unweighted sum of (a - b)^2 over all cells (step doubling's error estimate); synchronises.
+ * ------------------------------------------------------------------------------------------------ */
+typedef enum { MG_HEAT_EXPLICIT_EULER = 0, MG_HEAT_IMPLICIT_EULER = 1, MG_HEAT_CRANK_NICOLSON = 2, MG_HEAT_BDF2 = 3 } mg_heat_scheme;
+typedef struct mg_heat mg_heat;
+typedef struct mg_heat_step_info {
+  double lambda, rhs_norm, initial_residual, final_residual, solve_seconds; /* shift, ||f||_h, ||r|| before / after, mg_iterate's time */
+  int32_t cycles, converged;
+} mg_heat_step_info;
+int mg_heat_create(const mg_config* cfg, double alpha, mg_heat** out);
+int mg_heat_destroy(mg_heat* s);
+const char* mg_heat_last_error(const mg_heat* s);
+/* host arrays (nx, ny) of host_dtype <-> slot; blocking */
+int mg_heat_set_slot(mg_heat* s, int slot, const void* u_host, int host_dtype);
+int mg_heat_get_slot(mg_heat* s, int slot, void* u_host, int host_dtype);
+/* device arrays of `dtype` with pitch `ld` (elements) <-> slot; blocking */
+int mg_heat_set_slot_device(mg_heat* s, int slot, const void* u_dev, int ld, int dtype);
+int mg_heat_get_slot_device(mg_heat* s, int slot, void* u_dev, int ld, int dtype);
+/* the static source profile S (host array; NULL: no source, the S terms are not read) */
+int mg_heat_set_source(mg_heat* s, const void* profile_host_or_null, int host_dtype);
+int mg_heat_step(mg_heat* s, int scheme, double dt, int src, int prev, int dst, double g0, double g1,
+                 const double* edge4_or_null, int bc_before_solve, double tol, int max_cycles, mg_heat_step_info* info);
+int mg_heat_diff_norm(mg_heat* s, int slot_a, int slot_b, double* out);
+/* The stepper's kernels, call by call: fp64 device arrays (nx, ny) with pitch `ld` (elements, even), 16-byte aligned;
+ * asynchronous on `stream` (nullable); scratch >= mg_dev_scratch_bytes(); sums in a fixed order (same bits on every run).
+ *   rhs:  per interior cell, with lap = mg_op_apply(coeff = +1) bit for bit and exactly this association,
+ *           implicit Euler  (u + dt*(g1*S)) / (dt*a)
+ *           Crank-Nicolson  (2.0*((u + ((dt*a)*lap)/2) + (dt*((g0*S)+(g1*S)))/2)) / (dt*a)
+ *           BDF2            (4.0*u - u_prev)/(2*dt*a) + (g1*S)/a
+ *         and 0 on the ring; scheme MG_HEAT_EXPLICIT_EULER writes the whole step u + dt*((a*lap) + g0*S) with the ring of u.
+ *         src NULL evaluates the same with S = 0 and reads nothing.  *sumsq_dev (nullable) = sum of out^2 over all cells.
+ *         Rows 0 .. nx - 1 of out are stored as whole 16-byte vectors (a pad column ny < roundup(ny, 2) is written 0), nothing
+ *         else; out differs from every input (the kernel reads u across tile edges).
+ *   ring: the Dirichlet ring of u from edge4 (a HOST array), order and corners as above; the interior is untouched.
+ *   diff_sumsq: *sumsq_dev = sum of (a - b)^2 over all cells. */
+int mg_dev_heat_rhs(int scheme, int nx, int ny, int ld, double hx, double hy, double alpha, double dt,
+                    const double* u, const double* u_prev_or_null, const double* src_or_null, double g0, double g1,
+                    double* out, void* scratch, double* sumsq_dev_or_null, void* stream);
+int mg_dev_heat_ring(int nx, int ny, int ld, const double edge4[4], double* u, void* stream);
+int mg_dev_heat_diff_sumsq(int nx, int ny, int ld, const double* a, const double* b, void* scratch, double* sumsq_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

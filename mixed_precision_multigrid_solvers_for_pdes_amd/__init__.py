@@ -20,7 +20,8 @@ from .memory_manager import GPUMemoryManager, GPUMemoryPool
 from .multi_gpu import DecompositionType, DistributedMultigridSolver, MultiGPUManager, MultiGPUSolver
 from .facade import MixedPrecisionMultigrid, PoissonProblem, default_max_levels
 from . import applications, heat_equation
-from .heat_equation import HeatEquationConfig, HeatEquationSolver, TimeSteppingScheme
+from .heat_equation import HeatEquationConfig, HeatEquationSolver, SeparableSource, TimeSteppingScheme
+from .heat_device import DeviceHeatStepper
 from .applications import MultigridPreconditioner, PoissonSolver2D
 from .krylov import PCGEngine, PCGSolver
 
@@ -34,6 +35,6 @@ __all__ = [
     "SmoothingKernels", "TransferKernels", "MixedPrecisionKernels",
     "MixedPrecisionMultigrid", "PoissonProblem", "default_max_levels",
     "PoissonSolver2D", "MultigridPreconditioner", "applications", "heat_equation", "HeatEquationSolver",
-    "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver",
+    "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver", "SeparableSource", "DeviceHeatStepper",
 ]
 __version__ = "0.1.0"

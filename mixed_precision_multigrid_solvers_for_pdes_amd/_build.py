@@ -3,7 +3,8 @@
 Every csrc/*.hip translation unit is compiled to an object of its own (in parallel, and only when it or a header it includes
 is newer than its object), then linked.  mg_launch.hip is the one unit that instantiates the kernels of mg_kernels.hpp and
 mg_rb_kernels.hpp (minutes); the engine, the solve loop and the stateless ABI are host code (seconds), so an edit there
-rebuilds that unit alone.  mg_pcg.hip holds the Krylov outer loop with the kernels of mg_pcg_kernels.hpp, which no other unit includes."""
+rebuilds that unit alone.  mg_pcg.hip holds the Krylov outer loop with the kernels of mg_pcg_kernels.hpp, mg_heat.hip the time
+stepper with those of mg_heat_kernels.hpp; no other unit includes either header."""
 import os
 import shutil
 import subprocess
@@ -14,19 +15,21 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIBPATH = os.path.join(LIBDIR, "libmghip.so")
-SOURCES = [os.path.join(CSRC, n) for n in ("mg_launch.hip", "mg_engine.hip", "mg_solve.hip", "mg_dev.hip", "mg_plan.hip", "mg_tail.hip", "mg_pcg.hip")]
-HEADERS = [os.path.join(CSRC, n) for n in ("mg_kernels.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp")] + \
+SOURCES = [os.path.join(CSRC, n) for n in ("mg_launch.hip", "mg_engine.hip", "mg_solve.hip", "mg_dev.hip", "mg_plan.hip", "mg_tail.hip", "mg_pcg.hip", "mg_heat.hip")]
+HEADERS = [os.path.join(CSRC, n) for n in ("mg_kernels.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp",
+                                               "mg_heat_kernels.hpp")] + \
           [os.path.join(os.path.dirname(HERE), "include", "mghip.h")]
 DEPS = SOURCES + HEADERS
 # headers a unit does NOT include (directly or through another header; checked against hipcc -MM): editing them leaves its
 # object current
-_HOST_UNIT = ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp")      # mg_kernels.hpp comes with mg_host.hpp (types and constants)
-NOT_INCLUDED = {"mg_launch.hip": ("mg_tail_kernels.hpp", "mg_pcg_kernels.hpp"),
+_HOST_UNIT = ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp")    # mg_kernels.hpp comes with mg_host.hpp (types and constants)
+NOT_INCLUDED = {"mg_launch.hip": ("mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp"),
                 "mg_engine.hip": _HOST_UNIT, "mg_solve.hip": _HOST_UNIT, "mg_dev.hip": _HOST_UNIT,
-                "mg_tail.hip": ("mg_launch.hpp", "mg_pcg_kernels.hpp"),
-                "mg_pcg.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp"),
+                "mg_tail.hip": ("mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp"),
+                "mg_pcg.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_heat_kernels.hpp"),
+                "mg_heat.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp"),
                 "mg_plan.hip": ("mg_kernels.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp",
-                                "mg_pcg_kernels.hpp")}
+                                "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp")}
 # -ffp-contract=off: the kernels reproduce the reference's rounding sequence (no FMA contraction).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

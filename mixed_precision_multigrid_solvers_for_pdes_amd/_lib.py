@@ -57,6 +57,13 @@ class MgPcgStats(C.Structure):
                 ("true_residual", C.c_double), ("iterations", C.c_int32), ("status", C.c_int32)]
 
 
+class MgHeatStepInfo(C.Structure):
+    """mg_heat_step_info (include/mghip.h, "Time stepping")"""
+    _fields_ = [("lambda", C.c_double), ("rhs_norm", C.c_double), ("initial_residual", C.c_double),
+                ("final_residual", C.c_double), ("solve_seconds", C.c_double), ("cycles", C.c_int32), ("converged", C.c_int32)]
+
+
+MG_HEAT_EXPLICIT_EULER, MG_HEAT_IMPLICIT_EULER, MG_HEAT_CRANK_NICOLSON, MG_HEAT_BDF2 = 0, 1, 2, 3
 PCG_STATUS = {0: "converged", 1: "max_iterations", 2: "breakdown"}
 SWITCH_REASONS = {0: None, 1: "threshold", 2: "stagnation", 3: "fp32_floor", 4: "fp32_skipped"}
 
@@ -159,6 +166,19 @@ SIGNATURES = {
     "mg_dev_pcg_update": (_i, [_i] * 3 + [_vp] * 8),
     "mg_dev_pcg_dots": (_i, [_i] * 3 + [_vp] * 7),
     "mg_dev_pcg_scalars": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp]),
+    "mg_heat_create": (_i, [C.POINTER(MgConfig), _d, C.POINTER(_vp)]),
+    "mg_heat_destroy": (_i, [_vp]),
+    "mg_heat_last_error": (C.c_char_p, [_vp]),
+    "mg_heat_set_slot": (_i, [_vp, _i, _vp, _i]),
+    "mg_heat_get_slot": (_i, [_vp, _i, _vp, _i]),
+    "mg_heat_set_slot_device": (_i, [_vp, _i, _vp, _i, _i]),
+    "mg_heat_get_slot_device": (_i, [_vp, _i, _vp, _i, _i]),
+    "mg_heat_set_source": (_i, [_vp, _vp, _i]),
+    "mg_heat_step": (_i, [_vp, _i, _d, _i, _i, _i, _d, _d, _pd, _i, _d, _i, C.POINTER(MgHeatStepInfo)]),
+    "mg_heat_diff_norm": (_i, [_vp, _i, _i, _pd]),
+    "mg_dev_heat_rhs": (_i, [_i] * 4 + [_d] * 4 + [_vp] * 3 + [_d] * 2 + [_vp] * 4),
+    "mg_dev_heat_ring": (_i, [_i] * 3 + [_pd, _vp, _vp]),
+    "mg_dev_heat_diff_sumsq": (_i, [_i] * 3 + [_vp] * 5),
 }
 
 _lib = None

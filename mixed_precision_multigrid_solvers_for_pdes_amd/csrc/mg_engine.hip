@@ -580,6 +580,33 @@ int set_u_impl(mg_handle* h, const void* u0, int hdt) {
   return MG_OK;
 }
 
+// set_u_impl(u0 != NULL) for an initial guess that is already on the device: converted on the handle's stream instead of
+// uploaded, the same state changes, no synchronisation
+int set_u_device_impl(mg_handle* h, const void* u_dev, int ld, int dtype) {
+  if (!h || !u_dev || !valid_dtype(dtype) || ld < h->lv[0].ny)
+    return fail(h ? &h->err : nullptr, MG_ERR_INVALID_VALUE, "set_u_device_impl: bad argument");
+  HIPC(&h->err, hipSetDevice(h->cfg.device));
+  Level& v = h->lv[0];
+  if (h->cfg.precision == MG_PREC_ADAPTIVE && h->phase != MG_F64 && h->L() > 1) {
+    h->phase = MG_F64;
+    inject_rings_once(h, MG_F64);
+  }
+  const int dt = h->iterate_dtype();
+  h->norm_partials = 0;
+  h->iterate_zero = false;
+  d_convert(dtype, dt, u_dev, v.u[dt], v.nx, v.ny, ld, v.ld[dt], h->stream);
+  if (v.t[dt]) d_convert_ring(dt, dt, v.u[dt], v.t[dt], v.nx, v.ny, v.ld[dt], v.ld[dt], h->stream);
+  HIPC(&h->err, hipGetLastError());
+  return MG_OK;
+}
+
+// The caller of mg_set_rhs_device / mg_update_rhs_device states that the boundary ring of the fine right-hand side is zero
+// (a residual, the right-hand side of a time step).  mg_set_rhs_device leaves the ring's sum of squares unknown (< 0: it
+// would cost a host round trip), which keeps the solve loop off the cached up-leg norm and the speculative launches
+// (fine_norm and solve_begin in mg_solve.hip test ring_sumsq >= 0); mg_update_rhs_device keeps whatever is recorded.
+// With a zero ring the sum is known to be 0, and mg_iterate runs the loop mg_solve runs after a host upload.
+void rhs_ring_is_zero(mg_handle* h) { h->ring_sumsq[MG_F32] = h->ring_sumsq[MG_F64] = 0.0; }
+
 }  // namespace mgh
 
 using namespace mgh;

@@ -212,6 +212,11 @@ int download(std::string* err, void* host, int hdt, const void* dev, int ddt, in
              hipStream_t st);
 int set_rhs_impl(mg_handle* h, const void* rhs, int hdt);
 int set_u_impl(mg_handle* h, const void* u0, int hdt);
+// the device form of set_u_impl(u0 != NULL): `u_dev` is an (nx, ny) device array of `dtype` with pitch `ld` (elements);
+// asynchronous on the handle's stream.  For the units of the library that own an engine (mg_heat.hip)
+int set_u_device_impl(mg_handle* h, const void* u_dev, int ld, int dtype);
+// after mg_set_rhs_device: the ring of that right-hand side (and of every later mg_update_rhs_device) is zero, so its sum is 0
+void rhs_ring_is_zero(mg_handle* h);
 void inject_rings(mg_handle* h, int ph, bool only_shared = false);
 void inject_rings_once(mg_handle* h, int p);
 // `part` (level 0 only) splits the fused cycle for speculative launching: the FRONT part (down leg + the whole

@@ -17,6 +17,9 @@ What differs, on purpose:
     _compute_laplacian :430-442 up to rounding: a different association of the same five terms).
   * Source terms and boundary data are evaluated on whole coordinate arrays when the callable accepts them (the
     reference loops over points); scalar-only callables fall back to np.vectorize.
+  * HeatEquationSolver(device_resident=True) keeps the state on the device between steps (heat_device.DeviceHeatStepper,
+    DESIGN.md 5.2): uniform Dirichlet data and a SeparableSource only; it also runs TimeSteppingScheme.BDF2, which the
+    reference names (:30) and never implements.
 """
 import logging
 import time
@@ -90,19 +93,41 @@ def _on_arrays(fn, *args):
     return np.asarray(np.vectorize(fn, otypes=[np.float64])(*args), dtype=np.float64).reshape(shape)
 
 
+class SeparableSource:
+    """A source term f(x, y, t) = profile(x, y) * factor(t).  A callable like any other source term (the host path evaluates
+    it as one); the device-resident path uploads profile(x, y) once and passes factor(t) as a scalar per step."""
+
+    def __init__(self, profile: Callable[[float, float], float], factor: Callable[[float], float]):
+        self.profile = profile
+        self.factor = factor
+
+    def __call__(self, x, y, t):
+        return self.profile(x, y) * self.factor(t)
+
+
 class HeatEquationSolver:
     """du/dt = alpha Laplace(u) + f  (heat_equation.py:75-600), implicit steps by shifted multigrid on the GPU."""
 
     def __init__(self, config: HeatEquationConfig, grid: Grid, precision_manager: Optional[PrecisionManager] = None,
-                 device_id: int = 0, max_levels: int = 32, smoother: str = "jacobi"):
+                 device_id: int = 0, max_levels: int = 32, smoother: str = "jacobi", device_resident: bool = False):
         self.config = config
         self.grid = grid
         self.precision_manager = precision_manager or PrecisionManager()
         # heat_equation.py:101-106: max_iterations = 20, tolerance = 1e-10 (there for a solver that is never called)
         self.mg_max_iterations, self.mg_tolerance = 20, 1e-10
         sm, omega = (_lib.MG_JACOBI, 0.8) if smoother == "jacobi" else (_lib.MG_RBGS, 1.0)
-        self.mg_solver = MultigridEngine(grid.nx, grid.ny, tuple(float(v) for v in grid.domain), -1.0, max_levels, "V",
-                                         2, 2, sm, omega, device=device_id)
+        self.device_resident = bool(device_resident)
+        if self.device_resident:
+            self._check_device_resident_config()            # before any device call
+            from .heat_device import DeviceHeatStepper
+            self.stepper = DeviceHeatStepper(grid.nx, grid.ny, tuple(float(v) for v in grid.domain),
+                                             config.thermal_diffusivity, max_levels, sm, omega, device=device_id)
+            self.mg_solver = None
+            self._cur = 0                # slot of the current solution
+            self._bdf_prev = None        # (slot of the level before it, the dt that led from there to _cur)
+        else:
+            self.mg_solver = MultigridEngine(grid.nx, grid.ny, tuple(float(v) for v in grid.domain), -1.0, max_levels, "V",
+                                             2, 2, sm, omega, device=device_id)
         self.laplacian = LaplacianOperator(coefficient=1.0)
         self.current_time = 0.0
         self.current_solution = None
@@ -124,10 +149,17 @@ class HeatEquationSolver:
         self.current_time = 0.0
         self.solution_history = [self.current_solution.copy()]
         self.time_history = [0.0]
+        if self.device_resident:         # the one upload of a run (and the source profile, once)
+            self._cur, self._bdf_prev = 0, None
+            self.stepper.set_slot(0, self.current_solution)
+            src = self.config.source_term
+            self.stepper.set_source(None if src is None else _on_arrays(src.profile, self._x[:, None], self._y[None, :]))
         return self.current_solution
 
     # -- single steps ---------------------------------------------------------------------
     def explicit_euler_step(self, u_old, dt):                            # heat_equation.py:155-185
+        if self.device_resident:         # the same step on the stepper's slots (one upload, one download)
+            return self._single_time_step(u_old, dt, TimeSteppingScheme.EXPLICIT_EULER)
         h_min = min(self.grid.hx, self.grid.hy)
         dt_stable = h_min**2 / (4 * self.config.thermal_diffusivity)
         if dt > dt_stable:
@@ -139,6 +171,8 @@ class HeatEquationSolver:
         return u_new
 
     def implicit_euler_step(self, u_old, dt):                            # heat_equation.py:187-225
+        if self.device_resident:         # the same step on the stepper's slots (one upload, one download)
+            return self._single_time_step(u_old, dt, TimeSteppingScheme.IMPLICIT_EULER)
         alpha = self.config.thermal_diffusivity
         source = self._evaluate_source_term(self.current_time + dt)
         rhs = u_old + dt * source
@@ -150,6 +184,8 @@ class HeatEquationSolver:
         return u_new
 
     def crank_nicolson_step(self, u_old, dt):                            # heat_equation.py:227-266
+        if self.device_resident:         # the same step on the stepper's slots (one upload, one download)
+            return self._single_time_step(u_old, dt, TimeSteppingScheme.CRANK_NICOLSON)
         alpha = self.config.thermal_diffusivity
         lap_u_old = self._compute_laplacian(u_old)
         source_old = self._evaluate_source_term(self.current_time)
@@ -165,6 +201,11 @@ class HeatEquationSolver:
     def adaptive_time_stepping(self, u_old, dt_initial, error_tolerance=1e-4,
                                scheme=TimeSteppingScheme.CRANK_NICOLSON) -> Tuple[np.ndarray, float]:
         """Step doubling (heat_equation.py:268-330): one step of dt against two of dt/2, Richardson estimate."""
+        if self.device_resident:
+            self.stepper.set_slot(0, np.ascontiguousarray(u_old, dtype=np.float64))
+            self._cur, self._bdf_prev = 0, None
+            slot, dt = self._device_adaptive_step(dt_initial, error_tolerance, scheme)
+            return self.stepper.get_slot(slot), dt
         dt = dt_initial
         max_iterations = 10
         safety_factor = 0.8
@@ -190,6 +231,8 @@ class HeatEquationSolver:
                              error_tolerance=1e-4, save_interval=1) -> Dict[str, Any]:
         if self.current_solution is None:
             raise ValueError("Initial condition not set. Call set_initial_condition() first.")
+        if self.device_resident:
+            return self._device_solve_time_dependent(t_final, dt_initial, scheme, adaptive, error_tolerance, save_interval)
         if dt_initial is None:
             h_min = min(self.grid.hx, self.grid.hy)
             if scheme == TimeSteppingScheme.EXPLICIT_EULER:
@@ -220,6 +263,11 @@ class HeatEquationSolver:
                 "scheme": scheme.value, "adaptive": adaptive}
 
     def _single_time_step(self, u_old, dt, scheme):                      # heat_equation.py:419-428
+        if self.device_resident:         # a host array in, a host array out: one upload, one step on slots, one download
+            self.stepper.set_slot(0, np.ascontiguousarray(u_old, dtype=np.float64))
+            self._cur, self._bdf_prev = 0, None
+            self._device_step(0, 1, dt, scheme, self.current_time)
+            return self.stepper.get_slot(1)
         if scheme == TimeSteppingScheme.EXPLICIT_EULER:
             return self.explicit_euler_step(u_old, dt)
         if scheme == TimeSteppingScheme.IMPLICIT_EULER:
@@ -281,6 +329,111 @@ class HeatEquationSolver:
             if bc.boundary_type == BoundaryType.DIRICHLET and name in ("left", "right", "bottom", "top"):
                 edge, _, ex, ey = self._edge(name)
                 rhs[edge] = _on_arrays(bc.evaluate, ex, ey, t)
+
+
+    # -- device-resident path: the state lives in the stepper's slots ------------------
+    def _check_device_resident_config(self):
+        for location in ("left", "right", "bottom", "top"):
+            bc = self.config.boundary_conditions.get(location)
+            if bc is None or bc.boundary_type != BoundaryType.DIRICHLET:
+                raise ValueError(f"device_resident=True needs a Dirichlet condition on every edge ('{location}' is "
+                                 f"{'missing' if bc is None else bc.boundary_type.value})")
+        src = self.config.source_term
+        if src is not None and not isinstance(src, SeparableSource):
+            raise ValueError("device_resident=True needs source_term=None or a SeparableSource(profile, factor)")
+
+    def _edge_values(self, t):
+        """(left, right, bottom, top) at time t; each edge's Dirichlet value must be spatially uniform"""
+        out = []
+        for location in ("left", "right", "bottom", "top"):
+            _, _, ex, ey = self._edge(location)
+            v = _on_arrays(self.config.boundary_conditions[location].evaluate, ex, ey, t)
+            if float(np.max(v)) != float(np.min(v)):
+                raise ValueError(f"device_resident=True needs a spatially uniform Dirichlet value on the '{location}' edge")
+            out.append(float(v.flat[0]))
+        return tuple(out)
+
+    def _device_step(self, src, dst, dt, scheme, t, prev=None):
+        """one step from slot src at time t into slot dst (BDF2: prev is the slot of the level before src)"""
+        if scheme == TimeSteppingScheme.EXPLICIT_EULER:
+            h_min = min(self.grid.hx, self.grid.hy)
+            dt_stable = h_min**2 / (4 * self.config.thermal_diffusivity)
+            if dt > dt_stable:
+                logger.warning(f"Time step dt={dt:.2e} exceeds stability limit {dt_stable:.2e}")
+        elif scheme not in (TimeSteppingScheme.IMPLICIT_EULER, TimeSteppingScheme.CRANK_NICOLSON, TimeSteppingScheme.BDF2):
+            raise ValueError(f"Unsupported time stepping scheme: {scheme}")
+        if scheme == TimeSteppingScheme.BDF2 and prev is None:
+            scheme = TimeSteppingScheme.CRANK_NICOLSON       # the start: self-starting and second order
+        factor = self.config.source_term.factor if self.config.source_term is not None else (lambda t: 0.0)
+        info = self.stepper.step(scheme, dt, src, dst, prev if scheme == TimeSteppingScheme.BDF2 else None,
+                                 float(factor(t)), float(factor(t + dt)), self._edge_values(t + dt), False,
+                                 self.mg_tolerance, self.mg_max_iterations)
+        if scheme != TimeSteppingScheme.EXPLICIT_EULER:
+            self.helmholtz_stats.append((info["lambda"], info["cycles"], info["final_residual"]))
+        return info
+
+    def _free_slots(self, *used):
+        return [k for k in range(4) if k not in used]
+
+    def _device_adaptive_step(self, dt_initial, error_tolerance, scheme):
+        """step doubling on slots: old / full / half1 / half2, the error from diff_norm; returns (slot, dt)"""
+        if scheme == TimeSteppingScheme.BDF2:
+            raise ValueError("adaptive=True is not available with BDF2 (a multistep scheme needs a constant dt)")
+        old = self._cur
+        full, half1, half2 = self._free_slots(old)
+        dt, t = dt_initial, self.current_time
+        for _ in range(10):
+            self._device_step(old, full, dt, scheme, t)
+            self._device_step(old, half1, dt / 2, scheme, t)
+            self._device_step(half1, half2, dt / 2, scheme, t)       # the reference's clock stands still inside an attempt (:298-300)
+            if scheme in (TimeSteppingScheme.EXPLICIT_EULER, TimeSteppingScheme.IMPLICIT_EULER):
+                error_est = self.stepper.diff_norm(half2, full)
+                order = 1
+            else:
+                error_est = self.stepper.diff_norm(half2, full) / 3.0
+                order = 2
+            if error_est < error_tolerance:
+                return half2, dt
+            dt = max(dt / 4, dt * 0.8 * (error_tolerance / error_est) ** (1 / (order + 1)))
+        logger.warning("Adaptive time stepping failed to converge after 10 iterations")
+        return full, dt
+
+    def _device_solve_time_dependent(self, t_final, dt_initial, scheme, adaptive, error_tolerance, save_interval):
+        if adaptive and scheme == TimeSteppingScheme.BDF2:
+            raise ValueError("adaptive=True is not available with BDF2 (a multistep scheme needs a constant dt)")
+        if dt_initial is None:
+            h_min = min(self.grid.hx, self.grid.hy)
+            if scheme == TimeSteppingScheme.EXPLICIT_EULER:
+                dt_initial = 0.2 * h_min**2 / self.config.thermal_diffusivity
+            else:
+                dt_initial = 0.1 * h_min
+        dt = dt_initial
+        step_count = 0
+        start_time = time.time()
+        while self.current_time < t_final:
+            if self.current_time + dt > t_final:
+                dt = t_final - self.current_time
+            if adaptive and scheme != TimeSteppingScheme.EXPLICIT_EULER:
+                new, dt = self._device_adaptive_step(dt, error_tolerance, scheme)
+                self._bdf_prev = None
+            else:
+                prev = self._bdf_prev[0] if self._bdf_prev is not None and self._bdf_prev[1] == dt else None
+                new = self._free_slots(self._cur, prev)[0]
+                self._device_step(self._cur, new, dt, scheme, self.current_time, prev)
+                self._bdf_prev = (self._cur, dt)
+            self._cur = new
+            self.current_time += dt
+            step_count += 1
+            if step_count % save_interval == 0:
+                self.solution_history.append(self.stepper.get_slot(self._cur))
+                self.time_history.append(self.current_time)
+                self.dt_history.append(dt)
+        self.current_solution = self.stepper.get_slot(self._cur)
+        solve_time = time.time() - start_time
+        return {"solution_history": self.solution_history, "time_history": self.time_history,
+                "dt_history": self.dt_history, "final_solution": self.current_solution,
+                "final_time": self.current_time, "total_steps": step_count, "solve_time": solve_time,
+                "scheme": scheme.value, "adaptive": adaptive}
 
 
 def create_gaussian_initial_condition(center=(0.5, 0.5), width=0.1, amplitude=1.0):    # heat_equation.py:602-610

@@ -1,0 +1,407 @@
+"""The device-resident heat stepper (include/mghip.h "Time stepping", csrc/mg_heat.hip) on a GPU: its kernels call by call
+against the NumPy restatement tests/heat_device_reference.py (bit for bit on dyadic unit-square grids), one step with a fixed
+cycle count against the restatement's MGOracle solve, HeatEquationSolver(device_resident=True) against what pins the host path
+(the converged heat oracle, the reference's outputs in tests/golden/heat.npz, the exact amplification of a discrete eigenmode)
+and against the host path itself, with the transfers counted."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import mixed_precision_multigrid_solvers_for_pdes_amd as mg
+from mixed_precision_multigrid_solvers_for_pdes_amd import _lib
+from mixed_precision_multigrid_solvers_for_pdes_amd import heat_equation as H
+from oracle import mg_oracle as O
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import heat_device_reference as R                                                 # noqa: E402
+from heat_inputs import heat_cases, heat_config                                   # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 2
+UNIT = (0.0, 1.0, 0.0, 1.0)
+KERNEL_CASES = [((5, 5), UNIT), ((9, 130), UNIT), ((65, 129), UNIT), ((257, 131), UNIT), ((21, 13), (0.0, 1.5, -0.2, 0.5))]
+SCHEMES = [R.EXPLICIT, R.IMPLICIT, R.CN, R.BDF2]
+
+
+def rel(a, b):
+    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _lib_pitch(ny):
+    ld = C.c_int(0)
+    _lib.check(_lib.load().mg_pitch_elems(_lib.MG_F64, ny, C.byref(ld)))
+    return ld.value
+
+
+class Field:
+    """an (nx, ny) fp64 device field with pitch ld between NaN guard rows; the pad columns hold NaN as well (the canary)"""
+
+    def __init__(self, arr, ld):
+        nx, ny = arr.shape
+        host = np.full((nx + 2 * GUARD, ld), np.nan)
+        host[GUARD:GUARD + nx, :ny] = arr
+        self.nx, self.ny, self.ld = nx, ny, ld
+        self.t = _torch().from_numpy(host).cuda()
+        self.start = host.copy()
+        self.ptr = C.c_void_p(self.t[GUARD:].data_ptr())
+
+    def numpy(self):
+        return self.t.cpu().numpy()
+
+    def field(self):
+        return self.numpy()[GUARD:GUARD + self.nx, :self.ny]
+
+    def outside_untouched(self, first_free_col):
+        """guard rows and the columns >= first_free_col still hold their bits"""
+        now, start = self.numpy().view(np.uint64), self.start.view(np.uint64)
+        mask = np.ones(now.shape, dtype=bool)
+        mask[GUARD:GUARD + self.nx, :first_free_col] = False
+        return bool(np.all(now[mask] == start[mask]))
+
+
+def _scalar():
+    return _torch().full((1,), float("nan"), dtype=_torch().float64, device="cuda")
+
+
+def _scratch(nx, ny):
+    n = C.c_int64(0)
+    _lib.check(_lib.load().mg_dev_scratch_bytes(nx, ny, C.byref(n)))
+    return _torch().full((n.value // 8,), float("nan"), dtype=_torch().float64, device="cuda")
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _dyadic(shape, domain):
+    """unit square with nx - 1 and ny - 1 powers of two: spacings and their reciprocal squares are exact"""
+    return domain == UNIT and all((n - 1) & (n - 2) == 0 for n in shape)
+
+
+# ======================================================================================================================
+# 1. the kernels, call by call
+# ======================================================================================================================
+@pytest.mark.parametrize("with_source", [False, True], ids=["nosrc", "src"])
+@pytest.mark.parametrize("scheme", SCHEMES)
+@pytest.mark.parametrize("shape,domain", KERNEL_CASES, ids=["%dx%d" % c[0] for c in KERNEL_CASES])
+def test_rhs_kernel_equals_restatement(shape, domain, scheme, with_source):
+    lib = _lib.load()
+    nx, ny = shape
+    hx, hy = O.grid_spacing(nx, ny, domain)
+    ld = _lib_pitch(ny) + 4
+    rng = np.random.default_rng(nx * 1000 + ny + R.SCHEME_CODES[scheme])
+    u, up, S = (rng.standard_normal(shape) for _ in range(3))
+    alpha, dt, g0, g1 = 0.7, 0.01, 0.3, 1.25
+    want = R.rhs(scheme, u, dt, alpha, hx, hy, up, S if with_source else None, g0, g1)
+    runs = []
+    for _ in range(2):
+        fu, fp, fs, fo = Field(u, ld), Field(up, ld), Field(S, ld), Field(np.full(shape, np.nan), ld)
+        ss, scratch = _scalar(), _scratch(nx, ny)
+        _lib.check(lib.mg_dev_heat_rhs(R.SCHEME_CODES[scheme], nx, ny, ld, hx, hy, alpha, dt, fu.ptr, fp.ptr if scheme == R.BDF2 else None,
+                                       fs.ptr if with_source else None, g0, g1, fo.ptr, _p(scratch), _p(ss), None))
+        _torch().cuda.synchronize()
+        got = fo.field()
+        assert fo.outside_untouched((ny + 1) // 2 * 2)                 # nothing beyond roundup(ny, 2), nothing outside the nx rows
+        for f in (fu, fp, fs):
+            assert f.outside_untouched(0)                              # the inputs keep every bit
+        runs.append((got.copy(), float(ss.cpu()[0])))
+    got, total = runs[0]
+    if _dyadic(shape, domain):
+        np.testing.assert_array_equal(got, want)
+    else:
+        assert rel(got, want) < 1e-13
+    if scheme != R.EXPLICIT:
+        for ring in (got[0, :], got[-1, :], got[:, 0], got[:, -1]):
+            assert not ring.any()
+    else:
+        for sl in ((0, slice(None)), (-1, slice(None)), (slice(None), 0), (slice(None), -1)):
+            np.testing.assert_array_equal(got[sl], u[sl])
+    np.testing.assert_allclose(total, np.sum(got * got), rtol=1e-13)
+    assert runs[0][0].tobytes() == runs[1][0].tobytes() and runs[0][1] == runs[1][1]        # the same bits on every run
+
+
+def test_rhs_kernel_without_sumsq_and_on_a_stream():
+    lib = _lib.load()
+    nx, ny = 37, 70
+    ld = _lib_pitch(ny)
+    u = np.random.default_rng(9).standard_normal((nx, ny))
+    fu, fo = Field(u, ld), Field(np.full((nx, ny), np.nan), ld)
+    scratch = _scratch(nx, ny)
+    st = _torch().cuda.Stream()
+    with _torch().cuda.stream(st):
+        _lib.check(lib.mg_dev_heat_rhs(2, nx, ny, ld, 1 / 36, 1 / 69, 1.0, 0.01, fu.ptr, None, None, 0.0, 0.0, fo.ptr, _p(scratch), None,
+                                       C.c_void_p(st.cuda_stream)))
+    st.synchronize()
+    assert rel(fo.field(), R.rhs(R.CN, u, 0.01, 1.0, 1 / 36, 1 / 69)) < 1e-13
+
+
+@pytest.mark.parametrize("shape", [(5, 5), (9, 130), (257, 131), (3, 3)], ids=lambda s: "%dx%d" % s)
+def test_ring_kernel(shape):
+    lib = _lib.load()
+    nx, ny = shape
+    ld = _lib_pitch(ny) + 4
+    u = np.random.default_rng(nx + ny).standard_normal(shape)
+    f = Field(u, ld)
+    e4 = (C.c_double * 4)(1.5, -2.5, 3.5, -4.5)
+    _lib.check(lib.mg_dev_heat_ring(nx, ny, ld, e4, f.ptr, None))
+    _torch().cuda.synchronize()
+    got = f.field()
+    np.testing.assert_array_equal(got, R.set_ring(u.copy(), (1.5, -2.5, 3.5, -4.5)))
+    assert got[0, 0] == 3.5 and got[-1, 0] == 3.5 and got[0, -1] == -4.5 and got[-1, -1] == -4.5
+    np.testing.assert_array_equal(got[1:-1, 1:-1], u[1:-1, 1:-1])
+    assert f.outside_untouched(ny)
+
+
+@pytest.mark.parametrize("shape,domain", KERNEL_CASES, ids=["%dx%d" % c[0] for c in KERNEL_CASES])
+def test_diff_sumsq_kernel(shape, domain):
+    lib = _lib.load()
+    nx, ny = shape
+    ld = _lib_pitch(ny) + 4
+    rng = np.random.default_rng(7 * nx + ny)
+    a, b = rng.standard_normal(shape), rng.standard_normal(shape)
+    fa, fb, ss, scratch = Field(a, ld), Field(b, ld), _scalar(), _scratch(nx, ny)
+    vals = []
+    for _ in range(2):
+        _lib.check(lib.mg_dev_heat_diff_sumsq(nx, ny, ld, fa.ptr, fb.ptr, _p(scratch), _p(ss), None))
+        _torch().cuda.synchronize()
+        vals.append(float(ss.cpu()[0]))
+    np.testing.assert_allclose(vals[0], np.sum((a - b) ** 2), rtol=1e-13)
+    assert vals[0] == vals[1] and fa.outside_untouched(0) and fb.outside_untouched(0)
+
+
+# ======================================================================================================================
+# 2. the engine's device-side initial guess (set_u_device_impl, reached through mg_heat_step) against mg_set_solution
+# ======================================================================================================================
+@pytest.mark.parametrize("smoother,omega,code", [("jacobi", 0.8, _lib.MG_JACOBI), ("rbgs", 1.0, _lib.MG_RBGS)])
+@pytest.mark.parametrize("shape", [(33, 33), (65, 129)], ids=lambda s: "%dx%d" % s)
+def test_device_initial_guess_equals_host_set_solution_bit_for_bit(shape, smoother, omega, code):
+    """mg_heat_step(tol = 0, max_cycles = 2) hands the engine f and the guess on the device; MultigridEngine.set_rhs(f) +
+    set_solution(host copy) + iterate(0, 2) hands it the same bits from the host (f of implicit Euler equals the restatement
+    bit for bit on these dyadic grids, test 1).  The iterates agree bit for bit, so do the norms, and the guess's ring --
+    random Dirichlet data -- comes back untouched: the ring reached the ping-pong partner and every cached state was reset.
+    Run twice on one stepper with different guesses: the second solve must not see anything of the first."""
+    nx, ny = shape
+    hx, hy = O.grid_spacing(nx, ny, UNIT)
+    alpha, dt = 0.6, 3e-3
+    rng = np.random.default_rng(nx * ny)
+    levels = mg.default_max_levels(nx, ny)
+    with mg.DeviceHeatStepper(nx, ny, UNIT, alpha, levels, smoother, omega) as st, \
+            mg.MultigridEngine(nx, ny, UNIT, -1.0, levels, "V", 2, 2, code, omega) as eng:
+        eng.set_shift(R.lam(R.IMPLICIT, dt, alpha))
+        for _ in range(2):
+            u = rng.standard_normal(shape)
+            f = R.rhs(R.IMPLICIT, u, dt, alpha, hx, hy)
+            st.set_slot(0, u)
+            info = st.step(R.IMPLICIT, dt, 0, 1, tol=0.0, max_cycles=2)
+            got = st.get_slot(1)
+            eng.set_rhs(f)
+            eng.set_solution(u)
+            np.testing.assert_array_equal(eng.get_solution(), u)
+            r = eng.iterate(0.0, 2)
+            want = eng.get_solution()
+            assert got.tobytes() == want.tobytes()
+            assert info["initial_residual"] == r["initial_residual"] and info["final_residual"] == r["residual_history"][-1]
+            for sl in ((0, slice(None)), (-1, slice(None)), (slice(None), 0), (slice(None), -1)):
+                np.testing.assert_array_equal(got[sl], u[sl])
+
+
+# ======================================================================================================================
+# 3. one step against the restatement, fixed cycle count (no stopping decision enters)
+# ======================================================================================================================
+@pytest.mark.parametrize("smoother,omega", [("jacobi", 0.8), ("rbgs", 1.0)])
+@pytest.mark.parametrize("shape", [(33, 33), (65, 65), (129, 65)], ids=lambda s: "%dx%d" % s)
+def test_step_equals_restatement_with_a_fixed_cycle_count(shape, smoother, omega):
+    nx, ny = shape
+    rng = np.random.default_rng(nx + ny)
+    x, y = np.linspace(0, 1, nx), np.linspace(0, 1, ny)
+    smooth = np.sin(np.pi * x[:, None]) * np.cos(2 * np.pi * y[None, :])
+    u = smooth + 0.05 * rng.standard_normal(shape)
+    up = 1.01 * smooth + 0.05 * rng.standard_normal(shape)
+    S = np.cos(np.pi * x[:, None]) * np.sin(np.pi * y[None, :]) + 0.05 * rng.standard_normal(shape)
+    alpha, dt, g0, g1 = 0.6, 3e-3, 0.8, 0.7
+    edges = (0.25, -0.5, 0.75, 1.5)
+    with mg.DeviceHeatStepper(nx, ny, UNIT, alpha, 32, smoother, omega) as st:
+        st.set_slot(0, up); st.set_slot(1, u); st.set_source(S)
+        for scheme in (R.IMPLICIT, R.CN, R.BDF2):
+            for e4, before in ((edges, False), (edges, True), (None, False)):
+                prev = 0 if scheme == R.BDF2 else None
+                info = st.step(scheme, dt, 1, 2, prev, g0, g1, e4, before, tol=0.0, max_cycles=3)
+                want, winfo = R.step(scheme, u, dt, alpha, u_prev=up, S=S, g0=g0, g1=g1, edge4=e4, bc_before_solve=before,
+                                     tol=0.0, max_cycles=3, smoother=smoother, omega=omega)
+                got = st.get_slot(2)
+                key = (scheme, e4 is not None, before)
+                assert rel(got, want) <= 1e-12, key
+                assert info["cycles"] == 3 and not info["converged"] and info["lambda"] == winfo["lambda"], key
+                np.testing.assert_allclose(info["final_residual"], winfo["final_residual"], rtol=1e-9, err_msg=str(key))
+                np.testing.assert_allclose(info["rhs_norm"], winfo["rhs_norm"], rtol=1e-9, err_msg=str(key))
+                assert st.get_slot(1).tobytes() == u.tobytes() and st.get_slot(0).tobytes() == up.tobytes(), key
+                if e4 is None:                       # the ring of src is kept
+                    for sl in ((0, slice(None)), (-1, slice(None)), (slice(None), 0), (slice(None), -1)):
+                        np.testing.assert_array_equal(got[sl], u[sl])
+        # explicit: the kernel alone, and the difference norm of two slots
+        st.step(R.EXPLICIT, 1e-5, 1, 3, None, g0, g1, edges)
+        want, _ = R.step(R.EXPLICIT, u, 1e-5, alpha, S=S, g0=g0, edge4=edges)
+        assert rel(st.get_slot(3), want) <= 1e-13
+        np.testing.assert_allclose(st.diff_norm(3, 1), np.linalg.norm(want - u), rtol=1e-12)
+        # what the ABI refuses
+        for bad in (dict(src=1, dst=1), dict(src=1, dst=4), dict(src=-1, dst=2), dict(src=1, dst=2, prev=2, scheme=R.BDF2),
+                    dict(src=1, dst=2, scheme=R.BDF2), dict(src=1, dst=2, prev=0), dict(src=1, dst=2, dt=0.0),
+                    dict(src=1, dst=2, max_cycles=0), dict(src=1, dst=2, bc_before_solve=True)):
+            kw = dict(dict(scheme=R.CN, dt=dt), **bad)
+            with pytest.raises(ValueError, match="mg_heat_step"):
+                st.step(kw.pop("scheme"), kw.pop("dt"), kw.pop("src"), kw.pop("dst"), **kw)
+
+
+# ======================================================================================================================
+# 4. the class against what pins the host path
+# ======================================================================================================================
+@pytest.fixture(scope="module")
+def heat_golden():
+    return np.load(os.path.join(HERE, "golden", "heat.npz"))
+
+
+def _separable(cfg):
+    if cfg.source_term is not None:
+        cfg.source_term = H.SeparableSource(lambda x, y: np.sin(np.pi * x) * np.cos(2 * np.pi * y), lambda t: np.exp(-t))
+    return cfg
+
+
+@pytest.mark.parametrize("name", ["explicit33", "implicit17", "implicit33_src", "cn17"])
+def test_device_steps_equal_converged_oracle_and_reference(heat_golden, name):
+    n, alpha, scheme, _, steps, bc_kind, with_source = heat_cases()[name]
+    dt = float(heat_golden[f"{name}__dt"])
+    hs = H.HeatEquationSolver(_separable(heat_config(H, alpha, bc_kind, with_source)), mg.Grid(n, n), device_resident=True)
+    hs.set_initial_condition(heat_golden[f"{name}__u0"])
+    sch = H.TimeSteppingScheme(scheme)
+    worst_ref = 0.0
+    for k in range(steps):
+        prev = heat_golden[f"{name}__u{k}"]
+        hs.current_time = k * dt
+        u = hs._single_time_step(prev.copy(), dt, sch)
+        uo = R.converged_oracle_step(name, k, heat_golden, H)
+        assert rel(u, uo) < 1e-9, (name, k)
+        worst_ref = max(worst_ref, rel(u, heat_golden[f"{name}__u{k + 1}"]))
+    assert worst_ref < (1e-12 if scheme == "explicit_euler" else 5e-3), worst_ref
+    if scheme != "explicit_euler":
+        assert len(hs.helmholtz_stats) == steps and all(c <= 20 for _, c, _ in hs.helmholtz_stats)
+    hs.stepper.close()
+
+
+def test_device_adaptive_run_matches_reference(heat_golden):
+    cfg = heat_config(H, 1.0, "zero", False)
+    hs = H.HeatEquationSolver(cfg, mg.Grid(17, 17), device_resident=True)
+    hs.set_initial_condition()
+    res = hs.solve_time_dependent(0.02, 0.004, H.TimeSteppingScheme.CRANK_NICOLSON, adaptive=True, error_tolerance=2e-3)
+    assert res["total_steps"] == int(heat_golden["adaptive17__steps"])
+    np.testing.assert_allclose(res["dt_history"], heat_golden["adaptive17__dts"], rtol=1e-6)
+    assert abs(res["final_time"] - 0.02) < 1e-12
+    assert rel(res["final_solution"], heat_golden["adaptive17__final"]) < 1e-6
+    assert set(res) == {"solution_history", "time_history", "dt_history", "final_solution", "final_time", "total_steps",
+                        "solve_time", "scheme", "adaptive"}
+    assert hs.stepper.uploads == 1 and hs.stepper.downloads == res["total_steps"] + 1
+    with pytest.raises(ValueError):
+        H.HeatEquationSolver(cfg, mg.Grid(17, 17), device_resident=True).solve_time_dependent(0.1)
+    with pytest.raises(ValueError, match="BDF2"):
+        hs.solve_time_dependent(0.03, 0.004, H.TimeSteppingScheme.BDF2, adaptive=True)
+    hs.stepper.close()
+
+
+# ======================================================================================================================
+# 5. eigenmode at 257^2
+# ======================================================================================================================
+def _mode(n):
+    g = mg.Grid(n, n)
+    h = g.hx
+    mode = np.sin(np.pi * g.X) * np.sin(2 * np.pi * g.Y)
+    mode[0, :] = mode[-1, :] = mode[:, 0] = mode[:, -1] = 0.0
+    mu = (4 / h**2) * (np.sin(np.pi * h / 2) ** 2 + np.sin(2 * np.pi * h / 2) ** 2)
+    return g, mode, mu
+
+
+def test_device_eigenmode_amplification_257():
+    n, alpha, dt = 257, 0.7, 2e-3
+    g, mode, mu = _mode(n)
+    z = dt * alpha * mu
+    hs = H.HeatEquationSolver(H.HeatEquationConfig(thermal_diffusivity=alpha), g, device_resident=True)
+    hs.set_initial_condition(mode)
+    for scheme, factor in (("implicit_euler", 1 / (1 + z)), ("crank_nicolson", (1 - z / 2) / (1 + z / 2))):
+        u = hs._single_time_step(mode.copy(), dt, H.TimeSteppingScheme(scheme))
+        assert rel(u, factor * mode) < 1e-9, scheme
+        assert hs.helmholtz_stats[-1][1] <= 12
+        # the public step methods run the same step on the stepper
+        named = hs.implicit_euler_step if scheme == "implicit_euler" else hs.crank_nicolson_step
+        assert named(mode.copy(), dt).tobytes() == u.tobytes()
+    assert rel(hs.explicit_euler_step(mode.copy(), 1e-6), (1 - 1e-6 * alpha * mu) * mode) < 1e-12
+    # three BDF2 steps, each from the exact pair (c_{n-1}, c_n) * mode
+    c = [1.0, (1 - z / 2) / (1 + z / 2)]
+    for _ in range(3):
+        c.append((4 * c[-1] - c[-2]) / (3 + 2 * z))
+    st = hs.stepper
+    for k in range(1, 4):
+        st.set_slot(0, c[k - 1] * mode); st.set_slot(1, c[k] * mode)
+        info = st.step("bdf2", dt, 1, 2, 0, 0.0, 0.0, (0.0, 0.0, 0.0, 0.0))
+        assert rel(st.get_slot(2), c[k + 1] * mode) < 1e-9, k
+        assert info["converged"] and info["cycles"] <= 12 and info["lambda"] == 3.0 / (2 * dt * alpha)
+    st.close()
+
+
+def test_device_bdf2_run_starts_with_crank_nicolson_and_follows_the_recurrence():
+    """a fixed-dt BDF2 run of the class on the eigenmode: step 1 is Crank-Nicolson, steps 2.. follow the recurrence; each
+    solve leaves at most the 1e-9 the single steps are held to, and the recurrence is stable, so k steps stay within k * 1e-9"""
+    n, alpha, dt, steps = 65, 0.7, 2.0 ** -9, 5        # dt a power of two: the times add up exactly
+    g, mode, mu = _mode(n)
+    z = dt * alpha * mu
+    hs = H.HeatEquationSolver(H.HeatEquationConfig(thermal_diffusivity=alpha), g, device_resident=True)
+    hs.set_initial_condition(mode)
+    res = hs.solve_time_dependent(steps * dt, dt, H.TimeSteppingScheme.BDF2, adaptive=False)
+    c = [1.0, (1 - z / 2) / (1 + z / 2)]
+    while len(c) <= res["total_steps"]:
+        c.append((4 * c[-1] - c[-2]) / (3 + 2 * z))
+    lambdas = [s[0] for s in hs.helmholtz_stats]
+    assert lambdas[0] == 2.0 / (dt * alpha) and all(l == 3.0 / (2 * dt * alpha) for l in lambdas[1:])
+    for k, u in enumerate(res["solution_history"]):
+        assert rel(u, c[k] * mode) < max(k, 1) * 1e-9, k
+    assert res["total_steps"] == steps and res["scheme"] == "bdf2" and abs(res["final_time"] - steps * dt) < 1e-12
+    hs.stepper.close()
+    with pytest.raises(ValueError, match="Unsupported"):          # the host path keeps raising
+        host = H.HeatEquationSolver(H.HeatEquationConfig(thermal_diffusivity=alpha), g)
+        host.set_initial_condition(mode)
+        host._single_time_step(mode.copy(), dt, H.TimeSteppingScheme.BDF2)
+
+
+# ======================================================================================================================
+# 6. a 12-step fixed-dt Crank-Nicolson run at 65^2 against the host path, transfers counted
+# ======================================================================================================================
+def test_device_run_equals_host_run_and_counts_its_transfers():
+    n, alpha, dt, steps = 65, 0.5, 2.0 ** -10, 12      # dt a power of two: the times add up exactly
+    bcs = lambda: {k: H.BoundaryCondition(H.BoundaryType.DIRICHLET, H.create_time_dependent_boundary(a, 2.0))         # noqa: E731
+                   for k, a in (("left", 0.3), ("right", 0.0), ("bottom", -0.2), ("top", 0.1))}
+    src = lambda: H.SeparableSource(lambda x, y: np.sin(np.pi * x) * np.cos(2 * np.pi * y), lambda t: np.exp(-t))    # noqa: E731
+    cfg = lambda: H.HeatEquationConfig(alpha, H.create_gaussian_initial_condition((0.4, 0.55), 0.12, 1.0), src(), bcs())  # noqa: E731
+    out = {}
+    for resident in (False, True):
+        hs = H.HeatEquationSolver(cfg(), mg.Grid(n, n), device_resident=resident)
+        hs.set_initial_condition()
+        out[resident] = hs.solve_time_dependent(steps * dt, dt, H.TimeSteppingScheme.CRANK_NICOLSON, adaptive=False, save_interval=4)
+        if resident:
+            assert hs.stepper.uploads == 1 and hs.stepper.downloads == 4 and hs.stepper.source_uploads == 1
+            assert len(hs.helmholtz_stats) == steps
+            hs.stepper.close()
+    dev, host = out[True], out[False]
+    assert dev["total_steps"] == host["total_steps"] and len(dev["solution_history"]) == 1 + 3
+    assert len(dev["time_history"]) == 4 and len(dev["dt_history"]) == 3
+    assert abs(dev["final_time"] - steps * dt) < 1e-12
+    assert rel(dev["final_solution"], host["final_solution"]) < steps * 1e-9
+    for a, b in zip(dev["solution_history"], host["solution_history"]):
+        assert rel(a, b) < steps * 1e-9
