@@ -138,6 +138,84 @@ __device__ __forceinline__ void rb_exchange(Pack<T>* __restrict__ xb, int w, int
   below = (w < W - 1) ? xb[((w + 1) * 2 + 0) * 64 + lane] : zero_pack<T>();
 }
 
+// 16-byte load through a pointer the compiler has lost track of (rb_leg_body: the strip of an up leg), said to be global
+// memory so that it stays a global_load (a generic pointer would make it a flat_load, which also counts as an LDS access).
+template <typename T, bool NONTEMPORAL> __device__ __forceinline__ Pack<T> ldg_global(const T* p) {
+  typedef int v4i __attribute__((ext_vector_type(4)));
+  const __attribute__((address_space(1))) v4i* g = (const __attribute__((address_space(1))) v4i*)p;
+  const v4i v = NONTEMPORAL ? __builtin_nontemporal_load(g) : *g;
+  return *reinterpret_cast<const Pack<T>*>(&v);
+}
+
+// Measurement builds (-DMG_EXPERIMENTS -DMG_EXP_PATCH=n, profiles/README.md "patch staging"): 1 the former staging loop (one
+// load, a full wait and one LDS write per trip, the strip loads issued behind it), 2 the same loop behind the strip loads,
+// 3 no patch loads at all (the patch is zero: results are wrong by construction; the most any staging can gain).
+#if !defined(MG_EXPERIMENTS) && defined(MG_EXP_PATCH)
+#error "MG_EXP_* switches need -DMG_EXPERIMENTS (a measurement build, never the shipped library)"
+#endif
+#ifndef MG_EXP_PATCH
+#define MG_EXP_PATCH 0
+#endif
+
+// Staging of the PH x PW coarse patch under an up leg's region, in ONE global-memory round trip per thread: load() issues
+// all of a thread's patch loads (TRIPS of them, a compile-time count) into registers and is called AHEAD of the strip
+// loads; store() writes them to LDS and is called once the strip loads are in flight.  Loads return in order and the patch
+// is needed first, so the waits in store() are vmcnt(2 RPT + TRIPS - 1 - t) with the whole strip still outstanding -- the
+// former loop (load, vmcnt(0), LDS write, per trip, with nothing of the strip requested before its last trip) put 4-10
+// serial memory latencies in front of every workgroup's strip.
+// Every load is unconditional, so that no trip is scheduled behind the strip: an entry outside the coarse grid (guarded
+// body) loads from a clamped in-bounds address and is zeroed afterwards; for entries past the end of the patch (the partly
+// filled last trip) see valid().  Entry idx = threadIdx.x + t NTHR walks the patch in steps of NTHR = DR PW + DC entries: (row, column)
+// advance by (DR, DC) with one carry, no division per entry; the interior body keeps only the column and a 32-bit offset
+// from the patch's first coarse cell (a scalar base).
+template <typename TX, int PH, int PW, int NTHR, bool INT> struct PatchStage {
+  static constexpr int TRIPS = (PH * PW + NTHR - 1) / NTHR;
+  static constexpr int DR = NTHR / PW, DC = NTHR % PW;
+  static constexpr bool kPartial = TRIPS * NTHR != PH * PW;          // the last trip has lanes past the end of the patch
+  TX v[TRIPS];
+  // whether the thread's entry of trip t lies in the patch; if not (last trip only) the thread loads and writes its entry
+  // of trip t - 1 once more: the same value to the same place, and both the load and the LDS write stay unconditional
+  // (guarded by `valid` the compiler sinks the load into the branch of the write, behind the strip loads, with a vmcnt(0))
+  static __device__ __forceinline__ bool valid(int t) { return !(kPartial && t == TRIPS - 1) || (int)threadIdx.x < PH * PW - t * NTHR; }
+  __device__ __forceinline__ void load(const TX* __restrict__ e_coarse, const FusedArgs& a, int pic0, int pjc0) {
+    static_assert(!kPartial || TRIPS >= 2, "a partly filled last trip repeats the thread's entry of the trip before");
+    int pr = (int)threadIdx.x / PW, pc = (int)threadIdx.x - pr * PW;
+    if (INT) {
+      const TX* __restrict__ base = e_coarse + ((size_t)pic0 * a.ldc + pjc0);       // workgroup-uniform
+      int off = pr * a.ldc + pc, off_before = off;                                  // < PH ldc
+#pragma unroll
+      for (int t = 0; t < TRIPS; ++t) {
+        v[t] = base[valid(t) ? off : off_before];
+        off_before = off;
+        pc += DC; off += DR * a.ldc + DC;
+        if (pc >= PW) { pc -= PW; off += a.ldc - PW; }
+      }
+    } else {
+      int pr_before = pr, pc_before = pc;
+#pragma unroll
+      for (int t = 0; t < TRIPS; ++t) {
+        const int ic = pic0 + (valid(t) ? pr : pr_before), jc = pjc0 + (valid(t) ? pc : pc_before);
+        const bool in = ic >= 0 && ic < a.nxc && jc >= 0 && jc < a.nyc;
+        const TX x = e_coarse[(size_t)min(max(ic, 0), a.nxc - 1) * a.ldc + min(max(jc, 0), a.nyc - 1)];
+        v[t] = in ? x : TX(0);
+        pr_before = pr; pc_before = pc;
+        pr += DR; pc += DC;
+        if (pc >= PW) { pc -= PW; pr += 1; }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);            // all of them ahead of the strip loads (the scheduler otherwise mixes the last ones in)
+  }
+  __device__ __forceinline__ void store(TX* __restrict__ patch) const {
+    // the strip loads (rb_leg_body reads the strip through pointers the compiler cannot trace) stay ahead of this barrier, and the
+    // scheduler may not hoist anything that waits for the strip ahead of the writes
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) patch[(int)threadIdx.x + (valid(t) ? t : t - 1) * NTHR] = v[t];
+    __builtin_amdgcn_sched_barrier(0);
+  }
+};
+
 // INT: the region lies strictly inside the grid (and the coarse patch / restriction targets inside the coarse grid, the
 // tile inside the norm window): no per-cell guard survives; only the region's own edge rows are skipped.
 // NT (compile time -- behind a run-time flag the compiler merges the two stores and drops the hint): bit 0 non-temporal
@@ -175,24 +253,46 @@ __device__ __forceinline__ void rb_leg_body(const T* __restrict__ u, const T* __
 
   // ---- load: the whole strip at once -----------------------------------------------------------------------------
   const int pic0 = (ri0 >> 1) + a.ci_off, pjc0 = (rj0 >> 1) + a.cj_off;         // coarse cell of patch entry (0, 0)
-  if (PROLONG) {
+  auto staging_loop = [&]() {                    // measurement builds only (MG_EXP_PATCH 1, 2, 3)
     for (int idx = threadIdx.x; idx < PH * PW; idx += W * 64) {
       const int pr = idx / PW, pc = idx - pr * PW;
       const int ic = pic0 + pr, jc = pjc0 + pc;
-      patch[idx] = (INT || (ic >= 0 && ic < a.nxc && jc >= 0 && jc < a.nyc)) ? e_coarse[(size_t)ic * a.ldc + jc] : TX(0);
+      patch[idx] = (MG_EXP_PATCH == 3) ? TX(0) : (INT || (ic >= 0 && ic < a.nxc && jc >= 0 && jc < a.nyc)) ? e_coarse[(size_t)ic * a.ldc + jc] : TX(0);
     }
-  }
+  };
+  PatchStage<TX, PROLONG ? PH : 1, PROLONG ? PW : 1, W * 64, INT> pstage;
+  if constexpr (PROLONG && MG_EXP_PATCH == 0) pstage.load(e_coarse, a, pic0, pjc0);
+  if (PROLONG && (MG_EXP_PATCH == 1 || MG_EXP_PATCH == 3)) staging_loop();
+  // Up legs read the strip through pointers the compiler knows nothing about: loads through `u` / `rhs` themselves
+  // (__restrict__, read-only: free to move) it sinks behind the patch's LDS writes or behind the barrier -- the fp32 up leg
+  // then requests its strip only when the patch has arrived, and every up leg its rhs only after the interpolation.
+  // These stay where they are written: ahead of the compiler barrier in PatchStage::store().
+  const T* us = u;
+  const T* fs = rhs;
+  constexpr bool kPinned = PROLONG && MG_EXP_PATCH == 0;
+  if (kPinned) asm volatile("" : "+s"(us), "+s"(fs));
+  auto load_f = [&](size_t at) { return kPinned ? ldg_global<T, (NT & 4) != 0>(fs + at) : (NT & 4) ? ldg_nt(rhs + at) : ldg(rhs + at); };
+  auto load_u = [&](size_t at) { return kPinned ? ldg_global<T, (NT & 2) != 0>(us + at) : (NT & 2) ? ldg_nt(u + at) : ldg(u + at); };
   Pack<T> F[RPT], U[RPT];
 #pragma unroll
   for (int k = 0; k < RPT; ++k) {
     const int gi = ri0 + r_base + k;
     F[k] = zero_pack<T>();
     U[k] = zero_pack<T>();
-    if (INT || (gi >= 0 && gi < a.nx && col_in)) {
-      F[k] = (NT & 4) ? ldg_nt(rhs + (size_t)gi * a.ld + gj0) : ldg(rhs + (size_t)gi * a.ld + gj0);
-      if (!ZERO_INIT) U[k] = (NT & 2) ? ldg_nt(u + (size_t)gi * a.ld + gj0) : ldg(u + (size_t)gi * a.ld + gj0);
+    if (kPinned && !INT) {
+      // guarded up leg: the strip loads are unconditional too (a clamped in-grid address; cells outside the grid are zeroed
+      // with the interpolation, behind the barrier) -- behind branches the compiler cannot count them, and the LDS writes of the
+      // patch would wait for all but the last few of them
+      const size_t at = (size_t)min(max(gi, 0), a.nx - 1) * a.ld + min(max(gj0, 0), (a.nyv - 1) / N * N);
+      F[k] = load_f(at);
+      if (!ZERO_INIT) U[k] = load_u(at);
+    } else if (INT || (gi >= 0 && gi < a.nx && col_in)) {
+      F[k] = load_f((size_t)gi * a.ld + gj0);
+      if (!ZERO_INIT) U[k] = load_u((size_t)gi * a.ld + gj0);
     }
   }
+  if (PROLONG && MG_EXP_PATCH == 2) staging_loop();
+  if constexpr (PROLONG && !VAR && MG_EXP_PATCH == 0) pstage.store(patch);      // the strip is in flight: the patch arrives ahead of it
   // ---- VAR: face means of the lane's cells ------------------------------------------------------------------------
   constexpr int AVK = VAR ? RPT + 1 : 1, AHK = VAR ? RPT : 1, AHN = VAR ? N + 1 : 1;
   Pack<T> av[AVK];            // av[k]: faces between strip rows k - 1 and k (a(i-1/2) of row k, a(i+1/2) of row k - 1)
@@ -210,6 +310,7 @@ __device__ __forceinline__ void rb_leg_body(const T* __restrict__ u, const T* __
         RD[VAR ? k : 0] = ldg(rdiag + (size_t)gi * a.ld + gj0);
       }
     }
+    if constexpr (PROLONG && MG_EXP_PATCH == 0) pstage.store(patch);
     Pack<T> a_above, a_below;
     rb_exchange<T, W>(xbuf + (size_t)W * 2 * 64, w, lane, A[0], A[RPT - 1], a_above, a_below);      // buffer 1: the first sweep uses buffer 0
 #pragma unroll
@@ -265,6 +366,9 @@ __device__ __forceinline__ void rb_leg_body(const T* __restrict__ u, const T* __
 #pragma unroll
           for (int e = 0; e < N; ++e)
             if (ok[e]) U[k].v[e] = (T)((TS)U[k].v[e] + (TS)val[e]);
+        } else {                                          // outside the grid: the clamped strip load fetched some in-grid cell
+          F[k] = zero_pack<T>();
+          U[k] = zero_pack<T>();
         }
       }
     }
