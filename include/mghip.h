@@ -481,6 +481,8 @@ int mg_dev_pcg_scalars(int op, const double* partials_a, int na, const double* p
  *   explicit Euler: one kernel from src to dst, then the ring from edge4 if given; info is zero but for converged = 1.
  *   BDF2 is (3 u_new - 4 u + u_prev) / (2 dt) = alpha Laplace(u_new) + g1 S; the caller starts it (one Crank-Nicolson step).
  * mg_heat_diff_norm: sqrt of the unweighted sum of (a - b)^2 over all cells (step doubling's error estimate); synchronises.
+ *
+ * A diffusivity field (du/dt = alpha div(a grad u) + g S) and a conjugate-gradient inner solver: include/mghip_heat.h.
  * ------------------------------------------------------------------------------------------------ */
 typedef enum { MG_HEAT_EXPLICIT_EULER = 0, MG_HEAT_IMPLICIT_EULER = 1, MG_HEAT_CRANK_NICOLSON = 2, MG_HEAT_BDF2 = 3 } mg_heat_scheme;
 typedef struct mg_heat mg_heat;

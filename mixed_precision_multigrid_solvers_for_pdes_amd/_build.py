@@ -18,7 +18,7 @@ LIBPATH = os.path.join(LIBDIR, "libmghip.so")
 SOURCES = [os.path.join(CSRC, n) for n in ("mg_launch.hip", "mg_engine.hip", "mg_solve.hip", "mg_dev.hip", "mg_plan.hip", "mg_tail.hip", "mg_pcg.hip", "mg_heat.hip")]
 HEADERS = [os.path.join(CSRC, n) for n in ("mg_kernels.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp",
                                                "mg_heat_kernels.hpp")] + \
-          [os.path.join(os.path.dirname(HERE), "include", "mghip.h")]
+          [os.path.join(os.path.dirname(HERE), "include", n) for n in ("mghip.h", "mghip_heat.h")]
 DEPS = SOURCES + HEADERS
 # headers a unit does NOT include (directly or through another header; checked against hipcc -MM): editing them leaves its
 # object current
@@ -29,7 +29,7 @@ NOT_INCLUDED = {"mg_launch.hip": ("mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "
                 "mg_pcg.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_heat_kernels.hpp"),
                 "mg_heat.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp"),
                 "mg_plan.hip": ("mg_kernels.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp",
-                                "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp")}
+                                "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp", "mghip_heat.h")}
 # -ffp-contract=off: the kernels reproduce the reference's rounding sequence (no FMA contraction).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

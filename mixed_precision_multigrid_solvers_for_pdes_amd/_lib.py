@@ -64,6 +64,7 @@ class MgHeatStepInfo(C.Structure):
 
 
 MG_HEAT_EXPLICIT_EULER, MG_HEAT_IMPLICIT_EULER, MG_HEAT_CRANK_NICOLSON, MG_HEAT_BDF2 = 0, 1, 2, 3
+MG_HEAT_INNER_CYCLE, MG_HEAT_INNER_PCG = 0, 1
 PCG_STATUS = {0: "converged", 1: "max_iterations", 2: "breakdown"}
 SWITCH_REASONS = {0: None, 1: "threshold", 2: "stagnation", 3: "fp32_floor", 4: "fp32_skipped"}
 
@@ -181,6 +182,13 @@ SIGNATURES = {
     "mg_dev_heat_diff_sumsq": (_i, [_i] * 3 + [_vp] * 5),
 }
 
+# name -> (restype, argtypes); every symbol include/mghip_heat.h declares (the time stepper's extensions)
+HEAT_EXT_SIGNATURES = {
+    "mg_heat_create_ex": (_i, [C.POINTER(MgConfig), _d, _i, _i, _i, C.POINTER(_vp)]),
+    "mg_heat_set_coefficient": (_i, [_vp, _vp, _i]),
+    "mg_dev_heat_rhs_var": (_i, [_i] * 4 + [_d] * 4 + [_vp] * 4 + [_d] * 2 + [_vp] * 4),
+}
+
 _lib = None
 
 
@@ -226,7 +234,7 @@ def load():
                           "mixed_precision_multigrid_solvers_for_pdes_amd._build`")
     _share_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -1,11 +1,14 @@
-// The time stepper of libmghip.so: device-resident heat-equation steps  du/dt = alpha Laplace(u) + g(t) S(x, y)  (explicit and
-// implicit Euler, Crank-Nicolson, BDF2) on top of the multigrid engine (include/mghip.h, "Time stepping").  This unit
-// instantiates the kernels of mg_heat_kernels.hpp and holds the driver; the inner solver is an mg_handle of its own, driven
-// through the device entry points of the C ABI (mg_set_rhs_device / mg_update_rhs_device, mg_set_shift, mg_iterate,
-// mg_get_solution_device) on the engine's stream, where the stepper queues its own kernels too.
+// The time stepper of libmghip.so: device-resident heat-equation steps  du/dt = alpha div(a grad u) + g(t) S(x, y)  (explicit and
+// implicit Euler, Crank-Nicolson, BDF2; a == 1 unless mg_heat_set_coefficient gave a field) on top of the multigrid engine
+// (include/mghip.h, "Time stepping"; include/mghip_heat.h for the field and the PCG inner solver).  This unit instantiates the kernels of mg_heat_kernels.hpp and holds the driver; the
+// inner solver is an mg_handle of its own, driven through the device entry points of the C ABI (mg_set_rhs_device /
+// mg_update_rhs_device, mg_set_shift, mg_iterate, mg_get_solution_device) on the engine's stream, where the stepper queues its
+// own kernels too -- or an mg_pcg of its own (MG_HEAT_INNER_PCG), whose engine's stream then carries the stepper's work.
 //
 //   implicit step:  f = rhs(u_src [, u_prev]) and sum f^2  ->  engine rhs  ->  shift lambda  ->  initial guess u_src (or u_src
 //   with the new ring)  ->  cycles until ||r|| < tol max(1, ||f||)  ->  u_dst  [-> ring of u_dst]
+//   with PCG:       f and sum f^2  ->  shift lambda  ->  u_dst = the initial guess  ->  mg_pcg_solve_device(f, u_dst) to the same
+//   tolerance  [-> ring of u_dst]
 //
 // The state lives in four slots; a step reads one (two for BDF2) and writes another, so step doubling and multistep schemes
 // need no copy and no field crosses PCIe between steps.
@@ -20,12 +23,15 @@ constexpr int kSlots = 4;
 
 struct mg_heat {
   mg_config cfg;
-  mg_handle* eng = nullptr;
+  mg_handle* eng = nullptr;             // the inner engine: the stepper's own, or (inner == MG_HEAT_INNER_PCG) the one `pcg` owns
+  mg_pcg* pcg = nullptr;
+  int inner = MG_HEAT_INNER_CYCLE;
   int nx = 0, ny = 0, ld = 0;
   double hx = 0, hy = 0, alpha = 0;
   double* slot[kSlots] = {nullptr, nullptr, nullptr, nullptr};
   double* rhs = nullptr;
   double* src = nullptr;                // source profile S (nullable)
+  double* a = nullptr;                  // diffusivity field (nullable: the constant operator)
   double* partials = nullptr;
   double* d_sum = nullptr;              // device, one double
   double* h_sum = nullptr;              // pinned host
@@ -58,15 +64,20 @@ mg::TileGeom heat_geom(int nx, int ny, int ld) {
 
 // ---- launchers (shared by the driver and the stateless mg_dev_heat_* forms); an int result is the number of partials ----
 template <int SCHEME>
-int launch_rhs_scheme(const double* u, const double* u_prev, const double* src, double* out, double* partials,
+int launch_rhs_scheme(const double* u, const double* u_prev, const double* src, const double* a, double* out, double* partials,
                       const mg::TileGeom& g, const mg::HeatCoef& c, hipStream_t st) {
   auto k = src ? mg::heat_rhs_kernel<SCHEME, true> : mg::heat_rhs_kernel<SCHEME, false>;
-  hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, u, u_prev, src, out, partials, g, c);
+  if constexpr (SCHEME == mg::kHeatExplicit || SCHEME == mg::kHeatCn) {      // the schemes that evaluate the operator
+    if (a) k = src ? mg::heat_rhs_kernel<SCHEME, true, true> : mg::heat_rhs_kernel<SCHEME, false, true>;
+  }
+  hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, u, u_prev, src, a, out, partials, g, c);
   return g.ntiles;
 }
 
+// a: the diffusivity field or NULL (implicit Euler and BDF2 launch the same kernels either way: no operator in their f)
 int launch_rhs(int scheme, int nx, int ny, int ld, double hx, double hy, double alpha, double dt, const double* u,
-               const double* u_prev, const double* src, double g0, double g1, double* out, double* partials, hipStream_t st) {
+               const double* u_prev, const double* src, const double* a, double g0, double g1, double* out, double* partials,
+               hipStream_t st) {
   const mg::TileGeom g = heat_geom(nx, ny, ld);
   const Coef k = coefs(hx, hy);
   mg::HeatCoef c;
@@ -76,10 +87,10 @@ int launch_rhs(int scheme, int nx, int ny, int ld, double hx, double hy, double 
   c.two_dta = 2 * dt * alpha;
   c.g0 = g0; c.g1 = g1;
   switch (scheme) {
-    case MG_HEAT_EXPLICIT_EULER: return launch_rhs_scheme<mg::kHeatExplicit>(u, u_prev, src, out, partials, g, c, st);
-    case MG_HEAT_IMPLICIT_EULER: return launch_rhs_scheme<mg::kHeatImplicit>(u, u_prev, src, out, partials, g, c, st);
-    case MG_HEAT_CRANK_NICOLSON: return launch_rhs_scheme<mg::kHeatCn>(u, u_prev, src, out, partials, g, c, st);
-    default: return launch_rhs_scheme<mg::kHeatBdf2>(u, u_prev, src, out, partials, g, c, st);
+    case MG_HEAT_EXPLICIT_EULER: return launch_rhs_scheme<mg::kHeatExplicit>(u, u_prev, src, a, out, partials, g, c, st);
+    case MG_HEAT_IMPLICIT_EULER: return launch_rhs_scheme<mg::kHeatImplicit>(u, u_prev, src, a, out, partials, g, c, st);
+    case MG_HEAT_CRANK_NICOLSON: return launch_rhs_scheme<mg::kHeatCn>(u, u_prev, src, a, out, partials, g, c, st);
+    default: return launch_rhs_scheme<mg::kHeatBdf2>(u, u_prev, src, a, out, partials, g, c, st);
   }
 }
 
@@ -108,10 +119,16 @@ int eng_rc(mg_heat* s, int rc) {
   return rc;
 }
 #define ENG(call) do { const int rc_ = eng_rc(s, (call)); if (rc_ != MG_OK) return rc_; } while (0)
+int pcg_rc(mg_heat* s, int rc) {
+  if (rc != MG_OK) hfail(s, rc, std::string("inner solver: ") + mg_pcg_last_error(s->pcg));
+  return rc;
+}
+#define PCG(call) do { const int rc_ = pcg_rc(s, (call)); if (rc_ != MG_OK) return rc_; } while (0)
 
 void release(mg_heat* s) {
+  if (s->pcg) { (void)mg_pcg_destroy(s->pcg); s->pcg = nullptr; s->eng = nullptr; }      // the engine goes with its owner
   if (s->eng) { (void)mg_destroy(s->eng); s->eng = nullptr; }
-  for (double** p : {&s->slot[0], &s->slot[1], &s->slot[2], &s->slot[3], &s->rhs, &s->src, &s->partials, &s->d_sum})
+  for (double** p : {&s->slot[0], &s->slot[1], &s->slot[2], &s->slot[3], &s->rhs, &s->src, &s->a, &s->partials, &s->d_sum})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
   if (s->h_sum) { (void)hipHostFree(s->h_sum); s->h_sum = nullptr; }
 }
@@ -142,10 +159,36 @@ int implicit_step(mg_heat* s, int scheme, double dt, int src, int prev, int dst,
   const double dta = dt * s->alpha;
   const double lambda = scheme == MG_HEAT_IMPLICIT_EULER ? 1.0 / dta : scheme == MG_HEAT_CRANK_NICOLSON ? 2.0 / dta : 3.0 / (2 * dt * s->alpha);
   const int np = launch_rhs(scheme, s->nx, s->ny, s->ld, s->hx, s->hy, s->alpha, dt, s->slot[src], prev >= 0 ? s->slot[prev] : nullptr,
-                            s->src, g0, g1, s->rhs, s->partials, st);
+                            s->src, s->a, g0, g1, s->rhs, s->partials, st);
   launch_sum(s->partials, np, s->d_sum, st);
   HIPC(&s->err, hipGetLastError());
   HIPC(&s->err, hipMemcpyAsync(s->h_sum, s->d_sum, sizeof(double), hipMemcpyDeviceToHost, st));
+  if (s->pcg) {
+    // the conjugate-gradient loop iterates in place: dst := the initial guess (src, or src with the new ring), then the solve
+    if (lambda != s->lambda) { PCG(mg_pcg_set_shift(s->pcg, lambda)); s->lambda = lambda; }
+    HIPC(&s->err, hipMemcpyAsync(s->slot[dst], s->slot[src], field_bytes(s), hipMemcpyDeviceToDevice, st));
+    if (bc_before_solve) launch_ring(s->slot[dst], s->nx, s->ny, s->ld, edge4, st);
+    HIPC(&s->err, hipGetLastError());
+    HIPC(&s->err, hipStreamSynchronize(st));                      // sum f^2 has arrived
+    const double fnorm = std::sqrt(s->hx * s->hy * *s->h_sum);
+    if ((int)s->hist.size() < max_cycles) s->hist.resize(max_cycles);
+    int n = 0, conv = 0;
+    mg_pcg_stats stats;
+    PCG(mg_pcg_solve_device(s->pcg, s->rhs, s->ld, s->slot[dst], s->ld, MG_F64, tol * std::max(1.0, fnorm), max_cycles,
+                            s->hist.data(), max_cycles, &n, &conv, &stats));
+    if (!bc_before_solve && edge4) launch_ring(s->slot[dst], s->nx, s->ny, s->ld, edge4, st);
+    HIPC(&s->err, hipGetLastError());
+    if (info) {
+      info->lambda = lambda;
+      info->rhs_norm = fnorm;
+      info->initial_residual = stats.initial_residual;
+      info->final_residual = n > 0 ? s->hist[n - 1] : stats.initial_residual;
+      info->solve_seconds = stats.solve_seconds;
+      info->cycles = n;
+      info->converged = conv;                                      // a breakdown (stats.status == 2) ends the solve unconverged
+    }
+    return MG_OK;
+  }
   if (!s->eng_has_rhs) {
     ENG(mg_set_rhs_device(s->eng, s->rhs, s->ld, MG_F64));
     rhs_ring_is_zero(s->eng);      // f has a zero ring by construction: mg_iterate runs the loop mg_solve runs after an upload
@@ -190,18 +233,31 @@ int implicit_step(mg_heat* s, int scheme, double dt, int src, int prev, int dst,
 extern "C" {
 
 int mg_heat_create(const mg_config* cfg, double alpha, mg_heat** out) {
+  return mg_heat_create_ex(cfg, alpha, MG_HEAT_INNER_CYCLE, 0, 0, out);
+}
+
+int mg_heat_create_ex(const mg_config* cfg, double alpha, int inner, int num_cycles, int flexible, mg_heat** out) {
   if (!cfg || !out) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: NULL argument");
   *out = nullptr;
-  if (cfg->precision != MG_PREC_DOUBLE) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: the inner solver runs in MG_PREC_DOUBLE");
+  if (inner != MG_HEAT_INNER_CYCLE && inner != MG_HEAT_INNER_PCG) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: unknown inner solver");
+  if (inner == MG_HEAT_INNER_CYCLE && cfg->precision != MG_PREC_DOUBLE)
+    return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: the inner solver runs in MG_PREC_DOUBLE");
+  if (inner == MG_HEAT_INNER_PCG && cfg->precision != MG_PREC_DOUBLE && cfg->precision != MG_PREC_SINGLE_MANAGED &&
+      cfg->precision != MG_PREC_MIXED_LEVELS)
+    return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: the preconditioner of the PCG inner solver runs in MG_PREC_DOUBLE, MG_PREC_SINGLE_MANAGED or MG_PREC_MIXED_LEVELS");
   if (cfg->coeff != -1.0) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: coeff must be -1 (the steps solve (-Laplacian + lambda) u = f)");
   if (cfg->fmg_cycles != 0) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: fmg_cycles must be 0 (a step starts from the old time level)");
   if (!(alpha > 0.0) || !std::isfinite(alpha)) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_create: alpha must be finite and > 0");
   mg_handle* eng = nullptr;
-  int rc = mg_create(cfg, &eng);
+  mg_pcg* pcg = nullptr;
+  int rc = inner == MG_HEAT_INNER_PCG ? mg_pcg_create(cfg, num_cycles, flexible, &pcg) : mg_create(cfg, &eng);
   if (rc != MG_OK) return rc;
+  if (pcg) eng = pcg_engine(pcg);
   mg_heat* s = new mg_heat();
   s->cfg = *cfg;
   s->eng = eng;
+  s->pcg = pcg;
+  s->inner = inner;
   s->nx = cfg->nx; s->ny = cfg->ny;
   (void)mg_pitch_elems(MG_F64, cfg->ny, &s->ld);
   s->hx = eng->lv[0].hx; s->hy = eng->lv[0].hy;
@@ -273,6 +329,31 @@ int mg_heat_set_source(mg_heat* s, const void* profile_host_or_null, int host_dt
   return upload(s, s->src, profile_host_or_null, host_dtype);
 }
 
+int mg_heat_set_coefficient(mg_heat* s, const void* a_host_or_null, int host_dtype) {
+  if (!s || !valid_dtype(host_dtype)) return hfail(s, MG_ERR_INVALID_VALUE, "mg_heat_set_coefficient: bad argument");
+  if (a_host_or_null) {                                           // before any device work
+    const size_t n = (size_t)s->nx * s->ny;
+    bool ok = true;
+    if (host_dtype == MG_F64) { const double* p = (const double*)a_host_or_null; for (size_t k = 0; k < n && ok; ++k) ok = std::isfinite(p[k]) && p[k] > 0.0; }
+    else { const float* p = (const float*)a_host_or_null; for (size_t k = 0; k < n && ok; ++k) ok = std::isfinite(p[k]) && p[k] > 0.0f; }
+    if (!ok) return hfail(s, MG_ERR_INVALID_VALUE, "mg_heat_set_coefficient: the diffusivity field must be finite and > 0 everywhere");
+  }
+  HIPC(&s->err, hipSetDevice(s->cfg.device));
+  if (s->pcg) PCG(mg_pcg_set_coefficient(s->pcg, a_host_or_null, host_dtype));
+  else ENG(mg_set_coefficient(s->eng, a_host_or_null, host_dtype));
+  // what the inner solver cached for the old operator goes: the shift (and with it the reciprocal diagonals) is set again by
+  // the next implicit step, which hands the engine its right-hand side the way a first step does
+  s->lambda = -1.0;
+  s->eng_has_rhs = false;
+  if (!a_host_or_null) {
+    HIPC(&s->err, hipStreamSynchronize(s->eng->stream));
+    if (s->a) { (void)hipFree(s->a); s->a = nullptr; }
+    return MG_OK;
+  }
+  if (!s->a) { const int rc = alloc_zero(&s->err, (void**)&s->a, field_bytes(s), s->eng->stream); if (rc != MG_OK) return rc; }
+  return upload(s, s->a, a_host_or_null, host_dtype);
+}
+
 int mg_heat_step(mg_heat* s, int scheme, double dt, int src, int prev, int dst, double g0, double g1, const double* edge4_or_null,
                  int bc_before_solve, double tol, int max_cycles, mg_heat_step_info* info) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_heat_step: NULL stepper");
@@ -289,8 +370,8 @@ int mg_heat_step(mg_heat* s, int scheme, double dt, int src, int prev, int dst, 
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   if (scheme == MG_HEAT_EXPLICIT_EULER) {
     hipStream_t st = s->eng->stream;
-    (void)launch_rhs(scheme, s->nx, s->ny, s->ld, s->hx, s->hy, s->alpha, dt, s->slot[src], nullptr, s->src, g0, g1, s->slot[dst],
-                     s->partials, st);
+    (void)launch_rhs(scheme, s->nx, s->ny, s->ld, s->hx, s->hy, s->alpha, dt, s->slot[src], nullptr, s->src, s->a, g0, g1,
+                     s->slot[dst], s->partials, st);
     if (edge4_or_null) launch_ring(s->slot[dst], s->nx, s->ny, s->ld, edge4_or_null, st);
     HIPC(&s->err, hipGetLastError());
     if (info) { *info = mg_heat_step_info{}; info->converged = 1; }
@@ -317,16 +398,24 @@ int mg_heat_diff_norm(mg_heat* s, int slot_a, int slot_b, double* out) {
 int mg_dev_heat_rhs(int scheme, int nx, int ny, int ld, double hx, double hy, double alpha, double dt, const double* u,
                     const double* u_prev_or_null, const double* src_or_null, double g0, double g1, double* out, void* scratch,
                     double* sumsq_dev_or_null, void* stream) {
+  return mg_dev_heat_rhs_var(scheme, nx, ny, ld, hx, hy, alpha, dt, u, u_prev_or_null, src_or_null, nullptr, g0, g1, out, scratch,
+                             sumsq_dev_or_null, stream);
+}
+
+int mg_dev_heat_rhs_var(int scheme, int nx, int ny, int ld, double hx, double hy, double alpha, double dt, const double* u,
+                        const double* u_prev_or_null, const double* src_or_null, const double* a_or_null, double g0, double g1,
+                        double* out, void* scratch, double* sumsq_dev_or_null, void* stream) {
   CHECK_DEV(scheme >= MG_HEAT_EXPLICIT_EULER && scheme <= MG_HEAT_BDF2, "mg_dev_heat_rhs: unknown scheme");
   CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_heat_rhs: bad shape / pitch");
   CHECK_DEV(dt > 0.0 && std::isfinite(dt) && alpha > 0.0 && std::isfinite(alpha) && hx > 0.0 && hy > 0.0, "mg_dev_heat_rhs: dt, alpha and the spacings must be finite and > 0");
   CHECK_DEV(u && out && scratch, "mg_dev_heat_rhs: NULL pointer");
   CHECK_DEV(scheme != MG_HEAT_BDF2 || u_prev_or_null, "mg_dev_heat_rhs: BDF2 needs u_prev");
-  CHECK_DEV(!overlap(out, u, nx, ld) && !overlap(out, u_prev_or_null, nx, ld) && !overlap(out, src_or_null, nx, ld),
-            "mg_dev_heat_rhs: out is an array of its own (it overlaps an input)");
-  CHECK_DEV(aligned16(u) && aligned16(out) && aligned16(u_prev_or_null) && aligned16(src_or_null), "mg_dev_heat_rhs: unaligned pointer");
+  CHECK_DEV(!overlap(out, u, nx, ld) && !overlap(out, u_prev_or_null, nx, ld) && !overlap(out, src_or_null, nx, ld) &&
+            !overlap(out, a_or_null, nx, ld), "mg_dev_heat_rhs: out is an array of its own (it overlaps an input)");
+  CHECK_DEV(aligned16(u) && aligned16(out) && aligned16(u_prev_or_null) && aligned16(src_or_null) && aligned16(a_or_null),
+            "mg_dev_heat_rhs: unaligned pointer");
   const int n = launch_rhs(scheme, nx, ny, ld, hx, hy, alpha, dt, u, scheme == MG_HEAT_BDF2 ? u_prev_or_null : nullptr, src_or_null,
-                           g0, g1, out, (double*)scratch, (hipStream_t)stream);
+                           a_or_null, g0, g1, out, (double*)scratch, (hipStream_t)stream);
   if (sumsq_dev_or_null) launch_sum((double*)scratch, n, sumsq_dev_or_null, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;

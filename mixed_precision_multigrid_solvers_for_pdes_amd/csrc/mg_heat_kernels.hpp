@@ -5,8 +5,9 @@
 // aligned base.  Sums are per-workgroup partials (block_reduce_sum) followed by heat_reduce_kernel, a fixed-order pass of one
 // workgroup: no atomics, the same bits on every run.  Pad columns (>= ny) are masked out of the sums.
 //
-// Per step and cell: the right-hand side 2 words (u in, f out; 3 with u_prev for BDF2, one more with a source profile), the
-// ring a perimeter, the difference norm of step doubling 2 (a, b).
+// Per step and cell: the right-hand side 2 words (u in, f out; 3 with u_prev for BDF2, one more with a source profile, one
+// more with a diffusivity field where the scheme evaluates the operator), the ring a perimeter, the difference norm of step
+// doubling 2 (a, b).
 #pragma once
 
 #include "mg_kernels.hpp"
@@ -38,14 +39,23 @@ struct HeatCoef {
 //   16-byte loads, the stencil runs on the staged values).  The other two read u (and u_prev) straight into registers.
 //   Stored: rows 0 .. nx - 1 as whole 16-byte vectors up to column roundup(ny, 2) (a pad column there is written 0).  `out` is
 //   an array of its own: neighbouring workgroups read u across tile edges.
+//   VAR (explicit Euler and Crank-Nicolson only: the other two hold no operator): lap = L_a u = div(a grad u) with the vertex
+//   field `a`, whose tile + halo is staged in a second LDS array next to u's (2 x 18.5 KB per workgroup, as
+//   pcg_direction_kernel<true> and varcoef_kernel), in exactly their association:
+//     aip = 0.5*(a_c + a_dn), aim = 0.5*(a_c + a_up), ajp = 0.5*(a_c + a_e), ajm = 0.5*(a_c + a_w)
+//     lap = ((aip*dn + aim*up)*ihx2 + (ajp*ea + ajm*w)*ihy2) - uc*((aip + aim)*ihx2 + (ajp + ajm)*ihy2)
+//   The ring values of `a` are read (the faces next to the boundary).  One more word per cell.
 // --------------------------------------------------------------------------------------------
-template <int SCHEME, bool HAS_SRC>
+template <int SCHEME, bool HAS_SRC, bool VAR = false>
 __global__ __launch_bounds__(kBlock) void heat_rhs_kernel(const double* __restrict__ u, const double* __restrict__ u_prev,
-                                                          const double* __restrict__ src, double* __restrict__ out,
-                                                          double* __restrict__ partials, TileGeom g, HeatCoef c) {
+                                                          const double* __restrict__ src, const double* __restrict__ a,
+                                                          double* __restrict__ out, double* __restrict__ partials, TileGeom g,
+                                                          HeatCoef c) {
   using S = TileShape<double>;
   constexpr bool LAP = SCHEME == kHeatExplicit || SCHEME == kHeatCn;
+  static_assert(LAP || !VAR, "implicit Euler and BDF2 never read the diffusivity field");
   __shared__ __attribute__((aligned(16))) double s[LAP ? S::LDS_ELEMS : S::N];
+  __shared__ __attribute__((aligned(16))) double sa[VAR ? S::LDS_ELEMS : S::N];
   __shared__ double red[kBlock / 64];
   const int L = xcd_remap(blockIdx.x, g.ntiles);
   const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
@@ -67,13 +77,18 @@ __global__ __launch_bounds__(kBlock) void heat_rhs_kernel(const double* __restri
   }
   if (LAP) {
     stage_tile<double>(u, s, i0, j0, g.nx, g.nyv, g.ld);
+    if (VAR) stage_tile<double>(a, sa, i0, j0, g.nx, g.nyv, g.ld);
     __syncthreads();
   }
 
-  Pack<double> up = zero_pack<double>(), mid = up;
+  Pack<double> up = zero_pack<double>(), mid = up, aup = up, amid = up;
   if (LAP) {
     up = *reinterpret_cast<const Pack<double>*>(s + (lr + 0) * S::SJ + lc);
     mid = *reinterpret_cast<const Pack<double>*>(s + (lr + 1) * S::SJ + lc);
+  }
+  if (VAR) {
+    aup = *reinterpret_cast<const Pack<double>*>(sa + (lr + 0) * S::SJ + lc);
+    amid = *reinterpret_cast<const Pack<double>*>(sa + (lr + 1) * S::SJ + lc);
   }
   double acc = 0.0;
 #pragma unroll
@@ -87,6 +102,13 @@ __global__ __launch_bounds__(kBlock) void heat_rhs_kernel(const double* __restri
     } else {
       mid = uv[k];
     }
+    Pack<double> adn = zero_pack<double>();
+    double aleft = 0.0, aright = 0.0;
+    if (VAR) {
+      adn = *reinterpret_cast<const Pack<double>*>(sa + (lr + k + 2) * S::SJ + lc);
+      aleft = sa[(lr + k + 1) * S::SJ + lc - 1];
+      aright = sa[(lr + k + 1) * S::SJ + lc + S::N];
+    }
     const int gi = i0 + lr + k;
     const bool row_in = (gi >= 1) && (gi < g.nx - 1);
     Pack<double> o;
@@ -99,7 +121,18 @@ __global__ __launch_bounds__(kBlock) void heat_rhs_kernel(const double* __restri
       if (LAP) {
         const double w = (e == 0) ? left : mid.v[e - 1];
         const double ea = (e == S::N - 1) ? right : mid.v[e + 1];
-        lap = ((dn.v[e] + up.v[e]) * c.ihx2 + (ea + w) * c.ihy2) - uc * c.diag;
+        if (VAR) {
+          const double aw = (e == 0) ? aleft : amid.v[e - 1];
+          const double ae = (e == S::N - 1) ? aright : amid.v[e + 1];
+          const double aip = 0.5 * (amid.v[e] + adn.v[e]), aim = 0.5 * (amid.v[e] + aup.v[e]);
+          const double ajp = 0.5 * (amid.v[e] + ae), ajm = 0.5 * (amid.v[e] + aw);
+          const double sx = aip * dn.v[e] + aim * up.v[e];
+          const double sy = ajp * ea + ajm * w;
+          const double D0 = (aip + aim) * c.ihx2 + (ajp + ajm) * c.ihy2;
+          lap = (sx * c.ihx2 + sy * c.ihy2) - uc * D0;
+        } else {
+          lap = ((dn.v[e] + up.v[e]) * c.ihx2 + (ea + w) * c.ihy2) - uc * c.diag;
+        }
       }
       const double sc = HAS_SRC ? sv[k].v[e] : 0.0;
       double val, ring = 0.0;
@@ -122,6 +155,10 @@ __global__ __launch_bounds__(kBlock) void heat_rhs_kernel(const double* __restri
     if (LAP) {
       up = mid;
       mid = dn;
+    }
+    if (VAR) {
+      aup = amid;
+      amid = adn;
     }
   }
   const double t = block_reduce_sum(acc, red);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mghip.h"
+#include "../../include/mghip_heat.h"
 #include "mg_kernels.hpp"
 
 namespace mgh {
@@ -217,6 +218,9 @@ int set_u_impl(mg_handle* h, const void* u0, int hdt);
 int set_u_device_impl(mg_handle* h, const void* u_dev, int ld, int dtype);
 // after mg_set_rhs_device: the ring of that right-hand side (and of every later mg_update_rhs_device) is zero, so its sum is 0
 void rhs_ring_is_zero(mg_handle* h);
+// mg_pcg.hip: the preconditioner engine an mg_pcg owns (its stream carries all of the solver's work), for the unit of the
+// library that owns an mg_pcg (mg_heat.hip) and queues its own kernels in between
+mg_handle* pcg_engine(mg_pcg* s);
 void inject_rings(mg_handle* h, int ph, bool only_shared = false);
 void inject_rings_once(mg_handle* h, int p);
 // `part` (level 0 only) splits the fused cycle for speculative launching: the FRONT part (down leg + the whole

@@ -295,6 +295,10 @@ int solve_args_ok(mg_pcg* s, const char* who, const void* rhs, const void* out, 
 
 }  // namespace
 
+namespace mgh {
+mg_handle* pcg_engine(mg_pcg* s) { return s ? s->eng : nullptr; }
+}  // namespace mgh
+
 #define CHECK_DEV(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
 
 extern "C" {

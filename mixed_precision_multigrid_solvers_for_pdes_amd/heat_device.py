@@ -1,7 +1,8 @@
-"""Thin object wrapper of one mg_heat (include/mghip.h, "Time stepping"): heat-equation steps whose state stays on the device.
+"""Thin object wrapper of one mg_heat (include/mghip.h, "Time stepping"; include/mghip_heat.h): heat-equation steps whose state stays on the device.
 
 Four state slots (0..3); a step reads one slot (two for BDF2) and writes another.  Fields cross to the host only through
-set_slot / get_slot / set_source, which the object counts (`uploads`, `downloads`)."""
+set_slot / get_slot / set_source / set_coefficient, which the object counts (`uploads`, `downloads`, `source_uploads`,
+`coefficient_uploads`)."""
 import ctypes as C
 
 import numpy as np
@@ -11,6 +12,9 @@ from . import _lib
 SCHEMES = {"explicit_euler": _lib.MG_HEAT_EXPLICIT_EULER, "implicit_euler": _lib.MG_HEAT_IMPLICIT_EULER,
            "crank_nicolson": _lib.MG_HEAT_CRANK_NICOLSON, "bdf2": _lib.MG_HEAT_BDF2}
 NUM_SLOTS = 4
+INNER = {"cycle": _lib.MG_HEAT_INNER_CYCLE, "pcg": _lib.MG_HEAT_INNER_PCG}
+# the preconditioner's precision of the PCG inner solver (krylov.PRECISIONS); the state and the Krylov vectors are fp64
+PRECISIONS = {"double": _lib.MG_PREC_DOUBLE, "single_managed": _lib.MG_PREC_SINGLE_MANAGED, "mixed": _lib.MG_PREC_MIXED_LEVELS}
 
 
 def scheme_code(scheme):
@@ -24,12 +28,20 @@ def scheme_code(scheme):
 
 
 class DeviceHeatStepper:
-    """Owns an mg_heat: the inner multigrid engine (fp64, -Laplacian + lambda), the slots, the right-hand side and the source."""
+    """Owns an mg_heat: the inner solver of (-div(a grad) + lambda) u = f, the slots, the right-hand side, the source and
+    the diffusivity field.  inner="cycle": the plain multigrid cycle on an fp64 engine; inner="pcg": conjugate gradients
+    preconditioned by `num_cycles` cycles in `precision` ("double", "single_managed", "mixed"; the loop itself is fp64),
+    flexible as in PCGEngine (None: auto)."""
 
     def __init__(self, nx, ny, domain=(0.0, 1.0, 0.0, 1.0), alpha=1.0, max_levels=32, smoother=_lib.MG_JACOBI, omega=0.8,
                  device=0, cycle="V", pre=2, post=2, coarse_tol=1e-12, coarse_maxit=1000, fused=2, tail=True, speculate=True,
-                 coarse_direct=None):
+                 coarse_direct=None, inner="cycle", precision="double", num_cycles=1, flexible=None):
         from .engine import _direct_code
+        if inner not in INNER:                                   # before any device call
+            raise ValueError(f"inner must be one of {sorted(INNER)}, not {inner!r}")
+        if precision not in PRECISIONS or (inner == "cycle" and precision != "double"):
+            raise ValueError(f"precision must be one of {sorted(PRECISIONS)} with inner='pcg' (the preconditioner's) and "
+                             f"'double' with inner='cycle', not {precision!r}")
         lib = _lib.load()
         if isinstance(cycle, str):
             if cycle not in _lib.CYCLES:
@@ -39,16 +51,19 @@ class DeviceHeatStepper:
             smoother = {"jacobi": _lib.MG_JACOBI, "rbgs": _lib.MG_RBGS}[smoother]
         cfg = _lib.MgConfig(int(nx), int(ny), float(domain[0]), float(domain[1]), float(domain[2]), float(domain[3]),
                             -1.0, int(max_levels), int(cycle), int(pre), int(post), int(smoother), float(omega),
-                            float(coarse_tol), int(coarse_maxit), _lib.MG_PREC_DOUBLE, 1e-6, 4.0, 0, int(device), 0, 0,
+                            float(coarse_tol), int(coarse_maxit), PRECISIONS[precision], 1e-6, 4.0, 0, int(device), 0, 0,
                             int(fused), int(tail), 0, (2 if speculate is True else int(speculate)), _direct_code(coarse_direct), 0)
         self.cfg = cfg
         self._h = C.c_void_p(None)
         self._lib = lib
-        _lib.check(lib.mg_heat_create(C.byref(cfg), float(alpha), C.byref(self._h)))
+        _lib.check(lib.mg_heat_create_ex(C.byref(cfg), float(alpha), INNER[inner], int(num_cycles),
+                                         -1 if flexible is None else int(bool(flexible)), C.byref(self._h)))
         self.nx, self.ny, self.alpha = int(nx), int(ny), float(alpha)
+        self.inner, self.precision = inner, precision
         self.uploads = 0          # set_slot calls
         self.downloads = 0        # get_slot calls
         self.source_uploads = 0
+        self.coefficient_uploads = 0
 
     def _check(self, rc):
         if rc == _lib.MG_OK:
@@ -116,6 +131,15 @@ class DeviceHeatStepper:
         p = self._field(profile)
         self._check(self._lib.mg_heat_set_source(self._h, _lib.ptr(p), _lib.dtype_code(p.dtype)))
         self.source_uploads += 1
+
+    def set_coefficient(self, a):
+        """the diffusivity field a(x, y) > 0 on the grid: du/dt = alpha div(a grad u) + g S (None: back to a == 1)"""
+        if a is None:
+            self._check(self._lib.mg_heat_set_coefficient(self._h, None, _lib.MG_F64))
+            return
+        a = self._field(a)
+        self._check(self._lib.mg_heat_set_coefficient(self._h, _lib.ptr(a), _lib.dtype_code(a.dtype)))
+        self.coefficient_uploads += 1
 
     def step(self, scheme, dt, src, dst, prev=None, g0=1.0, g1=1.0, edges=None, bc_before_solve=False, tol=1e-10, max_cycles=20):
         """One step from slot `src` (and `prev` for BDF2) into slot `dst`; edges = (left, right, bottom, top) at t + dt or None.

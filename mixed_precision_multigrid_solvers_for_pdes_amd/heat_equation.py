@@ -20,6 +20,10 @@ What differs, on purpose:
   * HeatEquationSolver(device_resident=True) keeps the state on the device between steps (heat_device.DeviceHeatStepper,
     DESIGN.md 5.2): uniform Dirichlet data and a SeparableSource only; it also runs TimeSteppingScheme.BDF2, which the
     reference names (:30) and never implements.
+  * Device-resident only: conductivity= turns the equation into  du/dt = alpha div(a(x, y) grad u) + f  (transient conduction
+    through a composite; the reference has no counterpart), and inner_solver="pcg" solves the implicit systems by conjugate
+    gradients preconditioned with the multigrid cycle (inner_precision: the preconditioner's), which converges on jumping
+    coefficients where the plain cycle stalls.
 """
 import logging
 import time
@@ -106,22 +110,45 @@ class SeparableSource:
 
 
 class HeatEquationSolver:
-    """du/dt = alpha Laplace(u) + f  (heat_equation.py:75-600), implicit steps by shifted multigrid on the GPU."""
+    """du/dt = alpha Laplace(u) + f  (heat_equation.py:75-600), implicit steps by shifted multigrid on the GPU.
+    device_resident=True also takes conductivity= (a callable a(x, y) or an (nx, ny) array: du/dt = alpha div(a grad u) + f),
+    inner_solver="multigrid" | "pcg" and, for PCG, inner_precision="double" | "single_managed" | "mixed"."""
 
     def __init__(self, config: HeatEquationConfig, grid: Grid, precision_manager: Optional[PrecisionManager] = None,
-                 device_id: int = 0, max_levels: int = 32, smoother: str = "jacobi", device_resident: bool = False):
+                 device_id: int = 0, max_levels: int = 32, smoother: str = "jacobi", device_resident: bool = False,
+                 conductivity=None, inner_solver: str = "multigrid", inner_precision: str = "double"):
         self.config = config
         self.grid = grid
         self.precision_manager = precision_manager or PrecisionManager()
-        # heat_equation.py:101-106: max_iterations = 20, tolerance = 1e-10 (there for a solver that is never called)
-        self.mg_max_iterations, self.mg_tolerance = 20, 1e-10
-        sm, omega = (_lib.MG_JACOBI, 0.8) if smoother == "jacobi" else (_lib.MG_RBGS, 1.0)
+        if inner_solver not in ("multigrid", "pcg"):
+            raise ValueError(f"inner_solver must be 'multigrid' or 'pcg', not {inner_solver!r}")
         self.device_resident = bool(device_resident)
+        if not self.device_resident and (conductivity is not None or inner_solver == "pcg"):
+            raise ValueError("conductivity= and inner_solver='pcg' need device_resident=True (the host path steps "
+                             "du/dt = alpha Laplace(u) + f with the plain multigrid cycle)")
+        self.inner_solver, self.inner_precision = inner_solver, inner_precision
+        # heat_equation.py:101-106: max_iterations = 20, tolerance = 1e-10 (there for a solver that is never called); the
+        # conjugate-gradient loop needs 28-35 iterations on jumping coefficients (DESIGN.md 5.2.1)
+        self.mg_max_iterations, self.mg_tolerance = (60 if inner_solver == "pcg" else 20), 1e-10
+        sm, omega = (_lib.MG_JACOBI, 0.8) if smoother == "jacobi" else (_lib.MG_RBGS, 1.0)
+        self._x = np.linspace(grid.domain[0], grid.domain[1], grid.nx)   # heat_equation.py:134-135, 449-450, 501-502
+        self._y = np.linspace(grid.domain[2], grid.domain[3], grid.ny)
+        self.conductivity = None
+        if conductivity is not None:
+            a = (_on_arrays(conductivity, self._x[:, None], self._y[None, :]) if callable(conductivity)
+                 else np.array(conductivity, dtype=np.float64))
+            if a.shape != (grid.nx, grid.ny):
+                raise ValueError(f"conductivity shape {a.shape} doesn't match grid shape {(grid.nx, grid.ny)}")
+            if not np.all(np.isfinite(a)) or not np.all(a > 0):
+                raise ValueError("conductivity must be finite and > 0 everywhere")
+            self.conductivity = a
         if self.device_resident:
             self._check_device_resident_config()            # before any device call
             from .heat_device import DeviceHeatStepper
             self.stepper = DeviceHeatStepper(grid.nx, grid.ny, tuple(float(v) for v in grid.domain),
-                                             config.thermal_diffusivity, max_levels, sm, omega, device=device_id)
+                                             config.thermal_diffusivity, max_levels, sm, omega, device=device_id,
+                                             inner="pcg" if inner_solver == "pcg" else "cycle",
+                                             precision=inner_precision if inner_solver == "pcg" else "double")
             self.mg_solver = None
             self._cur = 0                # slot of the current solution
             self._bdf_prev = None        # (slot of the level before it, the dt that led from there to _cur)
@@ -133,8 +160,7 @@ class HeatEquationSolver:
         self.current_solution = None
         self.solution_history, self.time_history, self.dt_history = [], [], []
         self.helmholtz_stats = []        # per implicit solve: (lambda, cycles, final ||r||)
-        self._x = np.linspace(grid.domain[0], grid.domain[1], grid.nx)   # heat_equation.py:134-135, 449-450, 501-502
-        self._y = np.linspace(grid.domain[2], grid.domain[3], grid.ny)
+        self.step_converged = []         # per implicit solve of the device-resident path: did it meet the tolerance?
         logger.info(f"Initialized HeatEquationSolver: alpha={config.thermal_diffusivity}")
 
     # -- initial condition (heat_equation.py:120-153) -----------------------------------------
@@ -149,9 +175,11 @@ class HeatEquationSolver:
         self.current_time = 0.0
         self.solution_history = [self.current_solution.copy()]
         self.time_history = [0.0]
-        if self.device_resident:         # the one upload of a run (and the source profile, once)
+        if self.device_resident:         # the one upload of a run (and the source profile and the conductivity, once each)
             self._cur, self._bdf_prev = 0, None
             self.stepper.set_slot(0, self.current_solution)
+            if self.conductivity is not None:
+                self.stepper.set_coefficient(self.conductivity)
             src = self.config.source_term
             self.stepper.set_source(None if src is None else _on_arrays(src.profile, self._x[:, None], self._y[None, :]))
         return self.current_solution
@@ -357,7 +385,8 @@ class HeatEquationSolver:
         """one step from slot src at time t into slot dst (BDF2: prev is the slot of the level before src)"""
         if scheme == TimeSteppingScheme.EXPLICIT_EULER:
             h_min = min(self.grid.hx, self.grid.hy)
-            dt_stable = h_min**2 / (4 * self.config.thermal_diffusivity)
+            a_max = 1.0 if self.conductivity is None else float(np.max(self.conductivity))
+            dt_stable = h_min**2 / (4 * self.config.thermal_diffusivity * a_max)
             if dt > dt_stable:
                 logger.warning(f"Time step dt={dt:.2e} exceeds stability limit {dt_stable:.2e}")
         elif scheme not in (TimeSteppingScheme.IMPLICIT_EULER, TimeSteppingScheme.CRANK_NICOLSON, TimeSteppingScheme.BDF2):
@@ -370,6 +399,7 @@ class HeatEquationSolver:
                                  self.mg_tolerance, self.mg_max_iterations)
         if scheme != TimeSteppingScheme.EXPLICIT_EULER:
             self.helmholtz_stats.append((info["lambda"], info["cycles"], info["final_residual"]))
+            self.step_converged.append(info["converged"])
         return info
 
     def _free_slots(self, *used):
@@ -405,6 +435,8 @@ class HeatEquationSolver:
             h_min = min(self.grid.hx, self.grid.hy)
             if scheme == TimeSteppingScheme.EXPLICIT_EULER:
                 dt_initial = 0.2 * h_min**2 / self.config.thermal_diffusivity
+                if self.conductivity is not None:
+                    dt_initial /= float(np.max(self.conductivity))
             else:
                 dt_initial = 0.1 * h_min
         dt = dt_initial
