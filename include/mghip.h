@@ -38,8 +38,14 @@ typedef enum { MG_F32 = 0, MG_F64 = 1 } mg_dtype;
 typedef enum {
   MG_JACOBI = 0, /* weighted Jacobi            solvers/smoothers.py:41-86, solvers/iterative.py:72-108 */
   MG_RBGS = 1,   /* red-black Gauss-Seidel     solvers/smoothers.py:175-207                          */
-  MG_LEXGS = 2   /* lexicographic Gauss-Seidel solvers/smoothers.py:153-173 -- sequential by nature:
+  MG_LEXGS = 2,  /* lexicographic Gauss-Seidel solvers/smoothers.py:153-173 -- sequential by nature:
                     one workgroup sweeps anti-diagonals; exact, meant for small grids / the coarsest level */
+  /* zebra line relaxation for anisotropic grids (ours; include/mghip_line.h): colour 0 then colour 1 of the lines, every line a
+     tridiagonal solve.  Constant coefficients, one launch per operator (as MG_LEXGS), colour_offset 0; the coarsest level keeps
+     the lexicographic solve; mg_set_coefficient on such a handle returns MG_ERR_STATE */
+  MG_ZEBRA_X = 3,   /* lines along i at a fixed j: implicit in x, for hx < hy          */
+  MG_ZEBRA_Y = 4,   /* lines along j at a fixed i (contiguous): implicit in y, hy < hx */
+  MG_ZEBRA_ALT = 5  /* one sweep = an X sweep followed by a Y sweep                    */
 } mg_smoother_t;
 typedef enum { MG_CYCLE_V = 0, MG_CYCLE_W = 1, MG_CYCLE_F = 2 } mg_cycle_t;
 typedef enum {

@@ -11,7 +11,7 @@ from .operators import (BaseOperator, DiffusionOperator, HelmholtzOperator, Lapl
                         RestrictionOperator)
 from .precision import PrecisionLevel, PrecisionManager
 from .smoothers import (BaseSolver, ConvergenceHistory, EnhancedJacobiSolver, GaussSeidelSmoother,
-                        IterativeSolver, JacobiSmoother, WeightedJacobiSmoother)
+                        IterativeSolver, JacobiSmoother, LineRelaxationSmoother, WeightedJacobiSmoother)
 from .solver import GPUCommunicationAvoidingMultigrid, GPUMultigridSolver, MultigridCycle, MultigridSolver
 from .engine import MultigridEngine
 from .gpu_kernels import MixedPrecisionKernels, SmoothingKernels, TransferKernels
@@ -28,7 +28,7 @@ from .krylov import PCGEngine, PCGSolver
 __all__ = [
     "Grid", "BaseOperator", "LaplacianOperator", "DiffusionOperator", "HelmholtzOperator", "RestrictionOperator", "ProlongationOperator",
     "PrecisionLevel", "PrecisionManager", "BaseSolver", "ConvergenceHistory", "IterativeSolver",
-    "JacobiSmoother", "WeightedJacobiSmoother", "EnhancedJacobiSolver", "GaussSeidelSmoother",
+    "JacobiSmoother", "WeightedJacobiSmoother", "EnhancedJacobiSolver", "GaussSeidelSmoother", "LineRelaxationSmoother",
     "MultigridSolver", "GPUMultigridSolver", "GPUCommunicationAvoidingMultigrid", "MultigridCycle", "MultigridEngine",
     "GPUPrecisionManager", "GPUPrecisionLevel", "GPUMemoryManager", "GPUMemoryPool",
     "DistributedMultigridSolver", "MultiGPUSolver", "MultiGPUManager", "DecompositionType",

@@ -18,6 +18,7 @@ class PlanTimeout(RuntimeError):
     synchronise on it again -- report and leave (distributed.bench_main does, with os._exit)."""
 MG_F32, MG_F64 = 0, 1
 MG_JACOBI, MG_RBGS, MG_LEXGS = 0, 1, 2
+MG_ZEBRA_X, MG_ZEBRA_Y, MG_ZEBRA_ALT = 3, 4, 5      # zebra line relaxation (include/mghip_line.h)
 MG_CYCLE_V, MG_CYCLE_W, MG_CYCLE_F = 0, 1, 2
 MG_PREC_DOUBLE, MG_PREC_SINGLE, MG_PREC_MIXED_LEVELS, MG_PREC_ADAPTIVE, MG_PREC_SINGLE_MANAGED, MG_PREC_DEFECT = 0, 1, 2, 3, 4, 5
 
@@ -189,6 +190,15 @@ HEAT_EXT_SIGNATURES = {
     "mg_dev_heat_rhs_var": (_i, [_i] * 4 + [_d] * 4 + [_vp] * 4 + [_d] * 2 + [_vp] * 4),
 }
 
+# name -> (restype, argtypes); every symbol include/mghip_line.h declares (zebra line relaxation, call by call)
+LINE_SIGNATURES = {
+    "mg_line_plan_create": (_i, [_i] * 5 + [_d] * 3 + [C.POINTER(_vp)]),
+    "mg_line_plan_destroy": (_i, [_vp]),
+    "mg_dev_line_colour": (_i, [_vp, _i, _d, _vp, _vp, _vp]),
+    "mg_op_zebra": (_i, [_i] * 4 + [_d] * 4 + [_i] + [_vp] * 3),
+    "mg_line_time_sweep": (_i, [_vp, _i, _pd]),
+}
+
 _lib = None
 
 
@@ -234,7 +244,7 @@ def load():
                           "mixed_precision_multigrid_solvers_for_pdes_amd._build`")
     _share_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -160,6 +160,8 @@ class MultigridPreconditioner:                                         # precond
             raise NotImplementedError("the accelerated path implements bilinear prolongation")
         if smoother is None:       # the reference defaults to lexicographic GS; its parallel twin is red-black GS
             smoother = GaussSeidelSmoother(red_black=True)
+        if hasattr(smoother, "resolve"):               # LineRelaxationSmoother: "auto" against this grid, operator check
+            smoother.resolve(grid, operator)
         self.grid, self.operator = grid, operator
         prec = _lib.MG_PREC_SINGLE if np.dtype(grid.dtype) == np.float32 else _lib.MG_PREC_DOUBLE
         if self._engine is not None:

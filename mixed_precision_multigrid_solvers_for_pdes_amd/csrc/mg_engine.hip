@@ -72,6 +72,9 @@ static void release(mg_handle* h) {
     for (int d = 0; d < 2; ++d)
       for (void* p : {l.u[d], l.t[d], l.s[d], l.rhs[d], l.r[d], l.a[d], l.rd[d]})
         if (p) (void)hipFree(p);
+  for (auto& l : h->lv)
+    for (auto& per_dtype : l.lp)
+      for (mg_line_plan*& p : per_dtype) { line_plan_free(p); p = nullptr; }
   if (h->d_tail_ops) (void)hipFree(h->d_tail_ops);
   if (h->partials) (void)hipFree(h->partials);
   if (h->d_scalar) (void)hipFree(h->d_scalar);
@@ -124,6 +127,10 @@ static void smooth(mg_handle* h, int l, int nu) {
       for (int colour = 0; colour < 2; ++colour)
         d_rbgs_colour(dt, v.u[dt], v.rhs[dt], v.nx, v.ny, v.ld[dt], v.hx, v.hy, h->cfg.omega, colour,
                       h->cfg.colour_offset, h->stream, l == 0, h->sigma);
+    } else if (is_zebra(h->cfg.smoother)) {   // an X sweep, a Y sweep or both: colour 0 then colour 1 of the lines
+      for (int dir = 0; dir < 2; ++dir)
+        for (int colour = 0; colour < 2 && v.lp[dt][dir]; ++colour)
+          d_line_colour(v.lp[dt][dir], colour, h->cfg.omega, v.u[dt], v.rhs[dt], h->stream);
     } else {   // MG_LEXGS: exactly `nu` sweeps (tol < 0 never triggers the early exit)
       d_coarse(dt, v.u[dt], v.rhs[dt], v.nx, v.ny, v.ld[dt], v.hx, v.hy, h->cfg.coeff, h->cfg.omega, -1.0, nu - s,
                nullptr, h->stream, false, h->varcoef ? v.a[dt] : nullptr, h->sigma);
@@ -639,7 +646,11 @@ int mg_create(const mg_config* cfg, mg_handle** out) {
   if (cfg->nx < 3 || cfg->ny < 3)
     return fail(nullptr, MG_ERR_INVALID_VALUE, "Grid must have at least 3 points in each direction");   // core/grid.py:34-35
   if (cfg->cycle < MG_CYCLE_V || cfg->cycle > MG_CYCLE_F) return fail(nullptr, MG_ERR_INVALID_VALUE, "unknown cycle type");
-  if (cfg->smoother < MG_JACOBI || cfg->smoother > MG_LEXGS) return fail(nullptr, MG_ERR_INVALID_VALUE, "unknown smoother");
+  if (cfg->smoother < MG_JACOBI || cfg->smoother > MG_ZEBRA_ALT) return fail(nullptr, MG_ERR_INVALID_VALUE, "unknown smoother");
+  if (is_zebra(cfg->smoother) && cfg->colour_offset != 0)
+    return fail(nullptr, MG_ERR_INVALID_VALUE, "line smoothers serve a single domain: colour_offset must be 0");
+  if (is_zebra(cfg->smoother) && !line_shape_ok(cfg->smoother == MG_ZEBRA_Y ? 3 : cfg->nx, cfg->smoother == MG_ZEBRA_X ? 3 : cfg->ny))
+    return fail(nullptr, MG_ERR_INVALID_VALUE, "line smoothers: lines of more than 16384 cells do not fit a workgroup's LDS");
   if (cfg->precision < MG_PREC_DOUBLE || cfg->precision > MG_PREC_DEFECT) return fail(nullptr, MG_ERR_INVALID_VALUE, "unknown precision policy");
   if (cfg->pre < 0 || cfg->post < 0 || cfg->max_levels < 1 || cfg->coarse_maxit < 1)
     return fail(nullptr, MG_ERR_INVALID_VALUE, "negative sweep count / max_levels < 1 / coarse_maxit < 1");
@@ -689,6 +700,15 @@ int mg_create(const mg_config* cfg, mg_handle** out) {
       }
     }
   }
+  if (is_zebra(cfg->smoother))     // the smoothed levels own their plans, one per allocated dtype; the coarsest keeps its solve
+    for (int l = 0; l + 1 < h->L(); ++l) {
+      Level& v = h->lv[l];
+      for (int dt = 0; dt < 2; ++dt)
+        for (int dir = 0; dir < 2 && v.u[dt]; ++dir) {
+          if (cfg->smoother == (dir == 0 ? MG_ZEBRA_Y : MG_ZEBRA_X)) continue;
+          if ((rc = line_plan_make(dt, dir, v.nx, v.ny, v.ld[dt], v.hx, v.hy, 0.0, &v.lp[dt][dir], &h->err)) != MG_OK) return bail(rc);
+        }
+    }
   {
     const size_t np = max_partials(cfg->nx, cfg->ny);
     if ((rc = alloc_zero(&h->err, (void**)&h->partials, sizeof(double) * np, h->stream)) != MG_OK) return bail(rc);
@@ -819,6 +839,9 @@ int mg_set_rhs(mg_handle* h, const void* rhs, int host_dtype) {
 int mg_set_coefficient(mg_handle* h, const void* a_host, int host_dtype) {
   if (!h || !valid_dtype(host_dtype)) return fail(h ? &h->err : nullptr, MG_ERR_INVALID_VALUE, "mg_set_coefficient: bad argument");
   HIPC(&h->err, hipSetDevice(h->cfg.device));
+  if (a_host && is_zebra(h->cfg.smoother))
+    return fail(&h->err, MG_ERR_STATE, "mg_set_coefficient: the line smoothers relax the constant-coefficient operator (a variable "
+                                       "coefficient needs a matrix per line)");
   if (a_host && h->cfg.precision == MG_PREC_DEFECT)
     return fail(&h->err, MG_ERR_INVALID_VALUE, "mg_set_coefficient: defect correction (MG_PREC_DEFECT) runs the constant-coefficient operator");
   h->norm_partials = 0;
@@ -855,10 +878,18 @@ int mg_set_coefficient(mg_handle* h, const void* a_host, int host_dtype) {
 int mg_set_shift(mg_handle* h, double sigma) {
   if (!h || !(sigma >= 0.0) || !std::isfinite(sigma))
     return fail(h ? &h->err : nullptr, MG_ERR_INVALID_VALUE, "mg_set_shift: sigma must be finite and >= 0");
+  const bool changed = h->sigma != sigma;
   h->sigma = sigma;
   h->norm_partials = 0;     // a cached sum r^2 belongs to the previous operator
   HIPC(&h->err, hipSetDevice(h->cfg.device));
   refresh_rdiag(h);         // variable coefficients: the reciprocal diagonals carry the shift
+  if (changed && is_zebra(h->cfg.smoother)) {            // sigma is in the diagonal of every line's matrix: new tables
+    HIPC(&h->err, hipStreamSynchronize(h->stream));      // no launch in flight reads the old ones
+    for (auto& v : h->lv)
+      for (auto& per_dtype : v.lp)
+        for (mg_line_plan* p : per_dtype)
+          if (p) { const int rc = line_plan_set_sigma(p, sigma, &h->err); if (rc != MG_OK) return rc; }
+  }
   return MG_OK;
 }
 

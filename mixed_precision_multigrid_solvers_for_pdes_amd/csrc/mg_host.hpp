@@ -18,6 +18,8 @@
 #include "../../include/mghip_heat.h"
 #include "mg_kernels.hpp"
 
+struct mg_line_plan;   // mg_line.hip: the tables of one (dtype, direction, shape, spacings, sigma) of the zebra line smoothers
+
 namespace mgh {
 
 // The thread's last error message (mg_last_error(NULL)); the one definition is in mg_engine.hip.
@@ -111,6 +113,7 @@ struct Level {
   void* r[2] = {nullptr, nullptr};     // residual
   void* a[2] = {nullptr, nullptr};     // diffusion coefficient (variable-coefficient operator), else null
   void* rd[2] = {nullptr, nullptr};    // its reciprocal diagonal 1 / D per cell (var_rdiag_kernel): what the sweeps multiply by
+  mg_line_plan* lp[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // zebra line smoothers: plan per [dtype][0 X, 1 Y]
   double timings[3] = {0, 0, 0};       // smooth / restrict / prolong seconds (cfg.profile)
 };
 
@@ -204,6 +207,16 @@ namespace mgh {
 // hierarchy (and from which level) and fills h->tail2_*; tail2_launch runs one visit of that sub-cycle on h->stream.
 int tail2_plan(mg_handle* h);
 int tail2_launch(mg_handle* h, bool zero_top);
+
+// mg_line.hip: zebra line relaxation (mg_line_kernels.hpp).  dir: 0 X lines, 1 Y lines.  line_plan_set_sigma rebuilds the
+// tables in place: the caller has waited for every launch that reads them.  d_line_colour: one colour pass, in place.
+inline bool is_zebra(int sm) { return sm >= MG_ZEBRA_X && sm <= MG_ZEBRA_ALT; }
+bool line_shape_ok(int nx, int ny);
+int line_plan_make(int dtype, int dir, int nx, int ny, int ld, double hx, double hy, double sigma, mg_line_plan** out,
+                   std::string* err);
+void line_plan_free(mg_line_plan* p);
+int line_plan_set_sigma(mg_line_plan* p, double sigma, std::string* err);
+void d_line_colour(const mg_line_plan* p, int colour, double omega, void* u, const void* rhs, hipStream_t st);
 
 // mg_engine.hip: what the solve loop (mg_solve.hip) and the stateless ABI (mg_dev.hip) use of the handle and cycle driver.
 // hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which a

@@ -120,6 +120,9 @@ class DistributedMultigrid:
         self.torch = ops.torch
         self.domain, self.coeff = domain, coeff
         self.cycle_type, self.pre, self.post = cycle, pre, post
+        if smoother in ("line", "line_x", "line_y", "line_alternating", "zebra_x", "zebra_y", "zebra_alt"):
+            raise NotImplementedError("the decomposed (multi-GPU) solver has no line smoothers: a line would cross "
+                                      "sub-domains")                  # before any device work
         if smoother not in ("jacobi", "rbgs"):
             raise ValueError(f"Unknown smoother: {smoother}")
         if mode not in ("auto", "fused", "per_operator"):

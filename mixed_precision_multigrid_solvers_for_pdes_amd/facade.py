@@ -104,6 +104,10 @@ def _load_reference():
     return mod
 
 
+# zebra line relaxation (smoothers.LineRelaxationSmoother): smoother name -> direction
+LINE_SMOOTHERS = {"line": "auto", "line_x": "x", "line_y": "y", "line_alternating": "alternating"}
+
+
 class MixedPrecisionMultigrid:
     STRATEGIES = ("double", "single", "mixed", "adaptive", "adaptive_reference", "defect")
 
@@ -117,7 +121,7 @@ class MixedPrecisionMultigrid:
         torch.distributed, virtual ranks on one GPU otherwise -- and returns the single-GPU solve's iterate."""
         if precision_strategy not in self.STRATEGIES:
             raise ValueError(f"Unknown precision strategy: {precision_strategy}")
-        if smoother not in ("jacobi", "gauss_seidel", "red_black", "sor"):
+        if smoother not in ("jacobi", "gauss_seidel", "red_black", "sor") + tuple(LINE_SMOOTHERS):
             raise ValueError(f"Unknown smoother: {smoother}")
         self.precision_strategy = precision_strategy
         self.switch_threshold = switch_threshold
@@ -159,6 +163,10 @@ class MixedPrecisionMultigrid:
 
     def _smoother(self, mod=None):
         sm = (mod.solvers.smoothers if mod is not None else sys.modules[__package__ + ".smoothers"])
+        if self.smoother in LINE_SMOOTHERS:
+            if mod is not None:
+                raise NotImplementedError("the reference has no line relaxation; use_gpu=True")
+            return sm.LineRelaxationSmoother(LINE_SMOOTHERS[self.smoother], self.omega or 1.0)
         if self.smoother == "jacobi":
             if mod is not None:                          # NumPy-vectorised twin (iterative.py:72-108)
                 return mod.solvers.iterative.EnhancedJacobiSolver(relaxation_parameter=self.omega or 0.8)
@@ -177,6 +185,9 @@ class MixedPrecisionMultigrid:
             if self.precision_strategy in ("adaptive_reference", "defect") or self.use_fmg:
                 raise NotImplementedError("the decomposed solver runs the 'double', 'single', 'mixed' and 'adaptive' strategies "
                                           "without a full-multigrid start")
+            if self.smoother in LINE_SMOOTHERS:         # before any device work
+                raise NotImplementedError("the decomposed (multi-GPU) solver has no line smoothers: a line would cross "
+                                          "sub-domains; solve on one GPU")
             grid = problem.grid(dtype)
             name = {"jacobi": "jacobi", "gauss_seidel": "gauss_seidel", "red_black": "gauss_seidel", "sor": "sor"}[self.smoother]
             solver = DistributedMultigridSolver(device_ids=self.device_ids, decomposition_strategy=self.decomposition_strategy,

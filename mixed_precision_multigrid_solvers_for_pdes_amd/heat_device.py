@@ -48,7 +48,9 @@ class DeviceHeatStepper:
                 raise ValueError(f"unknown cycle type {cycle!r}")
             cycle = _lib.CYCLES[cycle]
         if isinstance(smoother, str):
-            smoother = {"jacobi": _lib.MG_JACOBI, "rbgs": _lib.MG_RBGS}[smoother]
+            from .smoothers import line_kind
+            hx, hy = (domain[1] - domain[0]) / (nx - 1), (domain[3] - domain[2]) / (ny - 1)
+            smoother = {"jacobi": _lib.MG_JACOBI, "rbgs": _lib.MG_RBGS, "line": line_kind(hx, hy)}[smoother]
         cfg = _lib.MgConfig(int(nx), int(ny), float(domain[0]), float(domain[1]), float(domain[2]), float(domain[3]),
                             -1.0, int(max_levels), int(cycle), int(pre), int(post), int(smoother), float(omega),
                             float(coarse_tol), int(coarse_maxit), PRECISIONS[precision], 1e-6, 4.0, 0, int(device), 0, 0,

@@ -130,7 +130,11 @@ class HeatEquationSolver:
         # heat_equation.py:101-106: max_iterations = 20, tolerance = 1e-10 (there for a solver that is never called); the
         # conjugate-gradient loop needs 28-35 iterations on jumping coefficients
         self.mg_max_iterations, self.mg_tolerance = (60 if inner_solver == "pcg" else 20), 1e-10
-        sm, omega = (_lib.MG_JACOBI, 0.8) if smoother == "jacobi" else (_lib.MG_RBGS, 1.0)
+        if smoother == "line":           # zebra lines along the strongly coupled direction (smoothers.LineRelaxationSmoother)
+            from .smoothers import line_kind
+            sm, omega = line_kind(grid.hx, grid.hy), 1.0
+        else:
+            sm, omega = (_lib.MG_JACOBI, 0.8) if smoother == "jacobi" else (_lib.MG_RBGS, 1.0)
         self._x = np.linspace(grid.domain[0], grid.domain[1], grid.nx)   # heat_equation.py:134-135, 449-450, 501-502
         self._y = np.linspace(grid.domain[2], grid.domain[3], grid.ny)
         self.conductivity = None

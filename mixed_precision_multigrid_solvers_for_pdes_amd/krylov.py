@@ -169,6 +169,8 @@ class PCGSolver:
             raise NotImplementedError("the accelerated path implements bilinear prolongation")
         if smoother is None:
             smoother = GaussSeidelSmoother(red_black=True)
+        if hasattr(smoother, "resolve"):               # LineRelaxationSmoother: "auto" against this grid, operator check
+            smoother.resolve(fine_grid, operator)
         if not isinstance(smoother, IterativeSolver) or smoother.kind is None:
             raise TypeError("smoother must be a JacobiSmoother / GaussSeidelSmoother (or subclass)")
         if smoother.kind == _lib.MG_LEXGS:

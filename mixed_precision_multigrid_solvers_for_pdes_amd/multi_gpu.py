@@ -131,6 +131,9 @@ class DistributedMultigridSolver(BaseSolver):
     def __init__(self, device_ids=None, decomposition_strategy="stripe", communication_method="p2p", agglomerate_at=1025,
                  ops_factory=None, **solver_kwargs):
         kw = dict(solver_kwargs)
+        if kw.get("smoother") in ("line", "line_x", "line_y", "line_alternating", "zebra_x", "zebra_y", "zebra_alt"):
+            raise NotImplementedError("the decomposed (multi-GPU) solver has no line smoothers: a line would cross "
+                                      "sub-domains")                  # before any device work
         super().__init__(kw.get("max_iterations", 100), kw.get("tolerance", 1e-6), False, "DistributedMultigrid")
         self.dist = _dist_if_initialised()
         self._ops_factory = ops_factory

@@ -198,3 +198,47 @@ class GaussSeidelSmoother(IterativeSolver):                                  # s
                                               float(getattr(operator, "coefficient", -1.0)), -1.0,
                                               int(num_iterations), _lib.ptr(u), _lib.ptr(rhs), _lib.ptr(out), None))
         return out
+
+
+def line_kind(hx, hy):
+    """the zebra kind whose lines run along the strongly coupled direction: hy <= hx -> Y lines, else X lines"""
+    return _lib.MG_ZEBRA_Y if hy <= hx else _lib.MG_ZEBRA_X
+
+
+class LineRelaxationSmoother(IterativeSolver):
+    """Zebra line relaxation for anisotropic grids (ours; the reference has point smoothers only): colour 0 then colour 1 of
+    the lines, every line one tridiagonal solve (include/mghip_line.h).  direction "x": lines along i, implicit in x, for
+    hx < hy; "y": lines along j, for hy < hx; "alternating": an X sweep followed by a Y sweep; "auto": "y" where hy <= hx,
+    else "x", resolved against the grid by setup() / smooth().  Relaxes -Laplace + shift (HelmholtzOperator); a
+    DiffusionOperator needs a matrix per line and raises NotImplementedError."""
+    DIRECTIONS = {"x": _lib.MG_ZEBRA_X, "y": _lib.MG_ZEBRA_Y, "alternating": _lib.MG_ZEBRA_ALT, "auto": None}
+
+    def __init__(self, direction="auto", relaxation_parameter=1.0, max_iterations=1000, tolerance=1e-8, verbose=False):
+        if direction not in self.DIRECTIONS:
+            raise ValueError(f"direction must be one of {sorted(self.DIRECTIONS)}, not {direction!r}")
+        super().__init__(max_iterations, tolerance, relaxation_parameter, verbose, "LineRelaxation")
+        self.direction = direction
+        self._kind = self.DIRECTIONS[direction]
+
+    @property
+    def kind(self):
+        if self._kind is None:
+            raise ValueError("LineRelaxationSmoother(direction='auto') is resolved against a grid: call resolve(grid) or setup()")
+        return self._kind
+
+    def resolve(self, grid, operator=None):
+        """fix "auto" for this grid; refuse operators the line solves do not serve"""
+        if operator is not None and hasattr(operator, "field"):
+            raise NotImplementedError("line relaxation serves constant coefficients: a DiffusionOperator needs a matrix per line")
+        if self.direction == "auto":
+            self._kind = line_kind(grid.hx, grid.hy)
+        return self._kind
+
+    def smooth(self, grid, operator, u, rhs, num_iterations=1):
+        kind = self.resolve(grid, operator)
+        u, rhs = self._prep(grid, u, rhs)
+        out = np.empty_like(u)
+        _lib.check(_lib.load().mg_op_zebra(_lib.dtype_code(u.dtype), kind, grid.nx, grid.ny, grid.hx, grid.hy,
+                                           float(getattr(operator, "shift", 0.0)), float(self.omega), int(num_iterations),
+                                           _lib.ptr(u), _lib.ptr(rhs), _lib.ptr(out)))
+        return out

@@ -82,6 +82,8 @@ class MultigridSolver(BaseSolver):
                 warnings.warn("MultigridSolver.setup(smoother=None) keeps the reference's default lexicographic "
                               "Gauss-Seidel smoother, which runs on one workgroup; pass "
                               "GaussSeidelSmoother(red_black=True) or a Jacobi smoother for the bandwidth-bound legs")
+        if hasattr(smoother, "resolve"):               # LineRelaxationSmoother: "auto" against this grid, operator check
+            smoother.resolve(fine_grid, operator)
         if not isinstance(smoother, IterativeSolver) or smoother.kind is None:
             raise TypeError("smoother must be a JacobiSmoother / GaussSeidelSmoother (or subclass)")
         if coarse_solver is not None and not (isinstance(coarse_solver, GaussSeidelSmoother) and not coarse_solver.red_black):
