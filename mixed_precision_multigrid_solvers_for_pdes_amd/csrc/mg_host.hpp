@@ -88,6 +88,20 @@ inline Coef coefs(double hx, double hy, double sigma = 0.0) {
   return c;
 }
 
+// Whether a register-blocked fp64 leg may evaluate its stencil in the exact-FMA forms of RowMath (mg_rb_kernels.hpp):
+//   sweep      un = fma(S, a, f) * invD                          for   nb = a (dn + up) + a (ea + wv);  un = (f + nb) * invD
+//   residual   r  = fma(-coeff a, fma(mid, -4, S), f)            for   r = f - coeff (((dn + up) a + (ea + wv) a) - mid D)
+// with S = (dn + up) + (ea + wv).  Constant coefficients without a shift, 1/hx^2 = 1/hy^2 = a = 2^p, D = 4 a and coeff = 0 or
+// +-2^k: every product of the plain forms is then a scaling by a power of two, which is exact and commutes with rounding, so
+// a s1 + a s2 = a rn(s1 + s2) and each FMA rounds exactly once where the plain form rounds once: the same bits for every
+// finite input, unless the plain form itself overflows on the way (|a S| beyond the largest double).  a >= 1 and
+// |coeff| a >= 1 keep every scaling from shrinking a value, so none of them can round in the subnormal range.
+inline bool pow2_stencil(const Coef& c, bool fp64, const void* acoef, double sigma, double coeff) {
+  int e = 0;
+  return fp64 && acoef == nullptr && sigma == 0.0 && c.all_pow2 && c.ihx2 == c.ihy2 && c.diag == 4.0 * c.ihx2 && c.ihx2 >= 1.0 &&
+         (coeff == 0.0 || (std::frexp(std::fabs(coeff), &e) == 0.5 && std::fabs(coeff) * c.ihx2 >= 1.0));
+}
+
 // min{x >= 0 : sqrt(x) >= tol}: "sqrt(x) < tol" and "x < sqrt_threshold(tol)" decide alike for every double x (IEEE sqrt is
 // correctly rounded, hence monotone) -- lets a latency-bound stop test skip the square root.  tol <= 0 never stops.
 inline double sqrt_threshold(double tol) {

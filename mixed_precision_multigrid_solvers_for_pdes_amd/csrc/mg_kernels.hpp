@@ -1704,6 +1704,7 @@ struct FusedArgs {
   int band;                     // spanning leg: tile rows per band (tiles are numbered down the columns of a band: see the kernel)
   int colour_offset;            // parity of the global index of local cell (0,0) (red-black colouring)
   int use_div;                  // 1: divide by the diagonal (1/D not exact)
+  int pow2;                     // register-blocked fp64 legs: 1 = the exact-FMA forms of RowMath (mg_host.hpp: pow2_stencil)
   int nxc, nyc, ldc;            // coarse level (restriction target / prolongation source)
   int ci_off, cj_off;           // coarse (ic, jc) <-> fine (2 (ic - ci_off), 2 (jc - cj_off)); 0 for whole grids
   int sides;                    // physical-boundary edges of this array (far-edge rule of the prolongation)
@@ -1714,6 +1715,7 @@ struct FusedArgs {
   int exp_flags;                // bit 3 (8): non-temporal stores of the output tile, bit 4 (16): non-temporal loads of u, bit 5 (32) of rhs
                                 // (set by the launcher for arrays that cannot stay in the 256 MiB Infinity Cache between two legs);
                                 // timing experiments (MG_EXP_FLAGS): 1 no XCD remap, 2 column-major tile order, 4 no interior body
+  double neg_coeff_a;           // pow2: -coeff / hx^2 (+-2^k), the one factor of the residual's outer FMA
 };
 
 // VAR: the variable-coefficient operator A = coeff * div(a grad .) (see varcoef_kernel above for the discretisation and

@@ -249,6 +249,7 @@ mg::FusedArgs fused_args(const LegGeom& g, bool use_div) {
   a.tiles_j = (g.ny - 1 + S::TJ - 1) / S::TJ;
   a.ntiles = tiles_i * a.tiles_j;
   a.nsweep = g.nsweep; a.nsweep2 = 0; a.band = 1; a.use_div = use_div ? 1 : 0; a.colour_offset = g.poff & 1;
+  a.pow2 = 0; a.neg_coeff_a = 0.0;
   a.nxc = g.nxc; a.nyc = g.nyc; a.ldc = g.ldc;
   a.ci_off = g.ci_off; a.cj_off = g.cj_off; a.sides = g.sides;
   a.ni_lo = 1; a.ni_hi = g.nx - 1; a.nj_lo = 1; a.nj_hi = g.ny - 1;
@@ -314,8 +315,11 @@ int launch_leg(const void* u, const void* rhs, void* out, const void* coarse, do
   constexpr int HALO = 2 * mg::sweep_halo(SM) + (LEG == kLegDown ? 2 : LEG == kLegUpNorm ? 1 : 0);
   const Coef c = coefs(g.hx, g.hy, g.sigma);
   mg::FusedArgs a;
-  if constexpr (FAM == kRegBlocked) a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
-  else a = fused_args<T, HALO, TI>(g, !c.pow2);
+  const double coeff = LEG == kLegSweeps ? 0.0 : g.coeff;
+  if constexpr (FAM == kRegBlocked) {
+    a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
+    if (pow2_stencil(c, sizeof(T) == 8, g.acoef, g.sigma, coeff)) { a.pow2 = 1; a.neg_coeff_a = -(coeff * c.ihx2); }
+  } else a = fused_args<T, HALO, TI>(g, !c.pow2);
   const bool nt = FAM == kRegBlocked && rb_stream(g, sizeof(T));
   auto pick = [&](auto zero) {
     constexpr bool Z = decltype(zero)::value;
@@ -333,7 +337,7 @@ int launch_leg(const void* u, const void* rhs, void* out, const void* coarse, do
   hipLaunchKernelGGL(k, dim3(a.ntiles), dim3(FAM == kRegBlocked ? W * 64 : mg::kFusedBlock), 0, st, (const T*)u, (const T*)rhs,
                      (T*)out, PROLONG ? (const TX*)coarse : nullptr, POST == mg::kPostRestrict ? (TX*)coarse : nullptr,
                      POST == mg::kPostNorm ? partials : nullptr, a, (T)c.ihx2, (T)c.ihy2, (T)c.invD, (T)c.diag, (T)g.omega,
-                     (T)(1.0 - g.omega), (T)(LEG == kLegSweeps ? 0.0 : g.coeff), (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
+                     (T)(1.0 - g.omega), (T)coeff, (const T*)g.acoef, (T)g.sigma, (const T*)g.rdiag);
   return POST == mg::kPostNorm ? a.ntiles : 0;
 }
 // the family and shape of a leg by level size
@@ -358,6 +362,7 @@ int launch_span_rb(const void* u, const void* rhs, void* out_mid, void* out_next
   const Coef c = coefs(g.hx, g.hy, g.sigma);
   mg::FusedArgs a = rb_args<T, HALO, W, RPT>(g, !c.pow2);
   a.nsweep2 = nsweep_pre;
+  if (pow2_stencil(c, sizeof(T) == 8, g.acoef, g.sigma, g.coeff)) { a.pow2 = 1; a.neg_coeff_a = -(g.coeff * c.ihx2); }
   static const int band = std::max(1, exp_env("MG_EXP_SPAN_BAND", 4));      // measurement builds: other band heights
   a.band = band;
   const bool nt = rb_stream(g, sizeof(T));

@@ -71,8 +71,19 @@ template <> __device__ __forceinline__ double dpp_from_upper_lane<double>(double
 template <typename T, int N> struct RowMath {
   // res = (1 - w) mid + w (f + ihx2 (dn + up) + ihy2 (east + west)) / D          (solvers/smoothers.py:62-84)
   static __device__ __forceinline__ Pack<T> relax(const Pack<T>& mid, const Pack<T>& dn, const Pack<T>& up, T left, T right,
-                                                  const Pack<T>& f, T ihx2, T ihy2, T invD, T D, T omega, T one_m_omega, bool use_div) {
+                                                  const Pack<T>& f, T ihx2, T ihy2, T invD, T D, T omega, T one_m_omega, bool use_div,
+                                                  bool pow2) {
     Pack<T> res;
+    if (pow2) {                       // ihx2 == ihy2 == 2^p: ihx2 S is exact, so the FMA rounds once where nb and f + nb round once
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const T wv = (e == 0) ? left : mid.v[e > 0 ? e - 1 : 0];
+        const T ea = (e == N - 1) ? right : mid.v[e < N - 1 ? e + 1 : 0];
+        const T un = __builtin_fma((dn.v[e] + up.v[e]) + (ea + wv), ihx2, f.v[e]) * invD;
+        res.v[e] = one_m_omega * mid.v[e] + omega * un;
+      }
+      return res;
+    }
 #pragma unroll
     for (int e = 0; e < N; ++e) {
       const T wv = (e == 0) ? left : mid.v[e > 0 ? e - 1 : 0];
@@ -85,8 +96,17 @@ template <typename T, int N> struct RowMath {
   }
   // r = f - coeff (((dn + up) ihx2 + (east + west) ihy2) - mid D)                 (operators/laplacian.py:73-77, 117-118)
   static __device__ __forceinline__ Pack<T> resid(const Pack<T>& mid, const Pack<T>& dn, const Pack<T>& up, T left, T right,
-                                                  const Pack<T>& f, T ihx2, T ihy2, T D, T coeff) {
+                                                  const Pack<T>& f, T ihx2, T ihy2, T D, T coeff, bool pow2, T neg_coeff_a) {
     Pack<T> r;
+    if (pow2) {                       // D == 4 ihx2, neg_coeff_a == -coeff ihx2 == -+2^k: both products are exact, one rounding each
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const T wv = (e == 0) ? left : mid.v[e > 0 ? e - 1 : 0];
+        const T ea = (e == N - 1) ? right : mid.v[e < N - 1 ? e + 1 : 0];
+        r.v[e] = __builtin_fma(neg_coeff_a, __builtin_fma(mid.v[e], T(-4), (dn.v[e] + up.v[e]) + (ea + wv)), f.v[e]);
+      }
+      return r;
+    }
 #pragma unroll
     for (int e = 0; e < N; ++e) {
       const T wv = (e == 0) ? left : mid.v[e > 0 ? e - 1 : 0];
@@ -101,7 +121,7 @@ template <> struct RowMath<float, 4> {
   typedef float f2 __attribute__((ext_vector_type(2)));
   static __device__ __forceinline__ Pack<float> relax(const Pack<float>& mid, const Pack<float>& dn, const Pack<float>& up, float left,
                                                       float right, const Pack<float>& f, float ihx2, float ihy2, float invD, float D,
-                                                      float omega, float one_m_omega, bool use_div) {
+                                                      float omega, float one_m_omega, bool use_div, bool /*pow2: fp64 only*/) {
     const f2 m0 = {mid.v[0], mid.v[1]}, m1 = {mid.v[2], mid.v[3]};
     const f2 sx0 = f2{dn.v[0], dn.v[1]} + f2{up.v[0], up.v[1]}, sx1 = f2{dn.v[2], dn.v[3]} + f2{up.v[2], up.v[3]};
     const f2 sy0 = f2{mid.v[1], mid.v[2]} + f2{left, mid.v[0]}, sy1 = f2{mid.v[3], right} + f2{mid.v[1], mid.v[2]};   // (east + west)
@@ -114,7 +134,8 @@ template <> struct RowMath<float, 4> {
     return res;
   }
   static __device__ __forceinline__ Pack<float> resid(const Pack<float>& mid, const Pack<float>& dn, const Pack<float>& up, float left,
-                                                      float right, const Pack<float>& f, float ihx2, float ihy2, float D, float coeff) {
+                                                      float right, const Pack<float>& f, float ihx2, float ihy2, float D, float coeff,
+                                                      bool /*pow2: fp64 only*/, float) {
     const f2 m0 = {mid.v[0], mid.v[1]}, m1 = {mid.v[2], mid.v[3]};
     const f2 sx0 = f2{dn.v[0], dn.v[1]} + f2{up.v[0], up.v[1]}, sx1 = f2{dn.v[2], dn.v[3]} + f2{up.v[2], up.v[3]};
     const f2 sy0 = f2{mid.v[1], mid.v[2]} + f2{left, mid.v[0]}, sy1 = f2{mid.v[3], right} + f2{mid.v[1], mid.v[2]};
@@ -250,6 +271,9 @@ __device__ __forceinline__ void rb_leg_body(const T* __restrict__ u, const T* __
   const int gj0 = rj0 + lane * N;
   const int r_base = w * RPT;
   const bool col_in = INT || (gj0 >= 0 && gj0 < a.nyv);
+  // the power-of-two forms of RowMath (FusedArgs::pow2): same bits as the plain ones, so the rim tiles' guarded body keeps those
+  const bool pow2 = INT && !VAR && a.pow2 != 0;
+  const T neg_coeff_a = (T)a.neg_coeff_a;
 
   // ---- load: the whole strip at once -----------------------------------------------------------------------------
   const int pic0 = (ri0 >> 1) + a.ci_off, pjc0 = (rj0 >> 1) + a.cj_off;         // coarse cell of patch entry (0, 0)
@@ -403,7 +427,7 @@ __device__ __forceinline__ void rb_leg_body(const T* __restrict__ u, const T* __
         const bool row_ok = INT ? ((k > 0 || w > 0) && (k < RPT - 1 || w < W - 1))
                                 : (r >= 1 && r < S::RI - 1 && gi >= 1 && gi < a.nx - 1);
         if (row_ok && !VAR) {
-          const Pack<T> res = RowMath<T, N>::relax(mid, dn, prev, left, right, F[k], ihx2, ihy2, invD, D, omega, one_m_omega, a.use_div != 0);
+          const Pack<T> res = RowMath<T, N>::relax(mid, dn, prev, left, right, F[k], ihx2, ihy2, invD, D, omega, one_m_omega, a.use_div != 0, pow2);
 #pragma unroll
           for (int e = 0; e < N; ++e) {
             const int gj = gj0 + e;
@@ -473,7 +497,7 @@ __device__ __forceinline__ void rb_leg_body(const T* __restrict__ u, const T* __
       const bool row_ok = INT ? ((k > 0 || w > 0) && (k < RPT - 1 || w < W - 1))
                               : (r >= 1 && r < S::RI - 1 && gi >= 1 && gi < a.nx - 1);
       if (wanted && row_ok && !VAR) {
-        const Pack<T> rr = RowMath<T, N>::resid(mid, dn, up, left, right, F[k], ihx2, ihy2, D, coeff);
+        const Pack<T> rr = RowMath<T, N>::resid(mid, dn, up, left, right, F[k], ihx2, ihy2, D, coeff, pow2, neg_coeff_a);
 #pragma unroll
         for (int e = 0; e < N; ++e) {
           const int gj = gj0 + e;

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""VGPR / LDS / occupancy of every kernel of libmghip's kernel-launch unit (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
+"""VGPR / scratch / LDS / occupancy of every kernel of libmghip's kernel-launch unit (hipcc -Rpass-analysis=kernel-resource-usage), one line each.
 
     python3 tools/kernel_resources.py [substring-of-mangled-name]
+
+MG_RES_OUT: where the throw-away library of the compile goes (default /tmp/_mg_res.so); set it to run two trees side by side.
 """
 import os
 import re
@@ -11,7 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "mixed_precision_multigrid_solvers_for_pdes_amd", "csrc", "mg_launch.hip")
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-       "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/_mg_res.so", SRC] + sys.argv[2:]
+       "-Rpass-analysis=kernel-resource-usage", "-o", os.environ.get("MG_RES_OUT", "/tmp/_mg_res.so"), SRC] + sys.argv[2:]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = {}
@@ -32,4 +34,4 @@ for name, r in sorted(rows.items()):
         short = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         short = re.sub(r"\(.*", "", short)[:110]
         print(f"{short:110s} vgpr {r.get('VGPRs'):>4s} agpr {r.get('AGPRs'):>3s} spill {r.get('VGPRs Spill'):>3s} "
-              f"lds {r.get('LDS Size [bytes/block]'):>6s} occ {r.get('Occupancy [waves/SIMD]')}")
+              f"scratch {r.get('ScratchSize [bytes/lane]'):>3s} lds {r.get('LDS Size [bytes/block]'):>6s} occ {r.get('Occupancy [waves/SIMD]')}")
