@@ -24,6 +24,7 @@ from .heat_equation import HeatEquationConfig, HeatEquationSolver, SeparableSour
 from .heat_device import DeviceHeatStepper
 from .applications import MultigridPreconditioner, PoissonSolver2D
 from .krylov import PCGEngine, PCGSolver
+from .eigen import EigenEngine, EigenSolver
 
 __all__ = [
     "Grid", "BaseOperator", "LaplacianOperator", "DiffusionOperator", "HelmholtzOperator", "RestrictionOperator", "ProlongationOperator",
@@ -36,5 +37,6 @@ __all__ = [
     "MixedPrecisionMultigrid", "PoissonProblem", "default_max_levels",
     "PoissonSolver2D", "MultigridPreconditioner", "applications", "heat_equation", "HeatEquationSolver",
     "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver", "SeparableSource", "DeviceHeatStepper",
+    "EigenEngine", "EigenSolver",
 ]
 __version__ = "0.1.0"

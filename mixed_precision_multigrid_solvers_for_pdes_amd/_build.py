@@ -4,8 +4,9 @@ Every csrc/*.hip translation unit is compiled to an object of its own (in parall
 is newer than its object), then linked.  mg_launch.hip is the one unit that instantiates the kernels of mg_kernels.hpp and
 mg_rb_kernels.hpp (minutes); the engine, the solve loop and the stateless ABI are host code (seconds), so an edit there
 rebuilds that unit alone.  mg_pcg.hip holds the Krylov outer loop with the kernels of mg_pcg_kernels.hpp, mg_heat.hip the time
-stepper with those of mg_heat_kernels.hpp, mg_line.hip the zebra line smoothers with the kernel of mg_line_kernels.hpp; no other
-unit includes any of these three headers."""
+stepper with those of mg_heat_kernels.hpp, mg_line.hip the zebra line smoothers with the kernel of mg_line_kernels.hpp, mg_eig.hip
+the block eigensolver with the kernels of mg_eig_kernels.hpp (and the host-only mg_eig_dense.hpp); no other unit includes any of
+these headers."""
 import os
 import shutil
 import subprocess
@@ -16,23 +17,25 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIBPATH = os.path.join(LIBDIR, "libmghip.so")
-SOURCES = [os.path.join(CSRC, n) for n in ("mg_launch.hip", "mg_engine.hip", "mg_solve.hip", "mg_dev.hip", "mg_plan.hip", "mg_tail.hip", "mg_pcg.hip", "mg_heat.hip", "mg_line.hip")]
+SOURCES = [os.path.join(CSRC, n) for n in ("mg_launch.hip", "mg_engine.hip", "mg_solve.hip", "mg_dev.hip", "mg_plan.hip", "mg_tail.hip", "mg_pcg.hip", "mg_heat.hip", "mg_line.hip", "mg_eig.hip")]
 HEADERS = [os.path.join(CSRC, n) for n in ("mg_kernels.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp",
-                                               "mg_heat_kernels.hpp", "mg_line_kernels.hpp")] + \
-          [os.path.join(os.path.dirname(HERE), "include", n) for n in ("mghip.h", "mghip_heat.h", "mghip_line.h")]
+                                               "mg_heat_kernels.hpp", "mg_line_kernels.hpp", "mg_eig_kernels.hpp", "mg_eig_dense.hpp")] + \
+          [os.path.join(os.path.dirname(HERE), "include", n) for n in ("mghip.h", "mghip_heat.h", "mghip_line.h", "mghip_eig.h")]
 DEPS = SOURCES + HEADERS
 # headers a unit does NOT include (directly or through another header; checked against hipcc -MM): editing them leaves its
 # object current
 _LINE = ("mg_line_kernels.hpp", "mghip_line.h")           # only mg_line.hip includes these
-_HOST_UNIT = ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE    # mg_kernels.hpp comes with mg_host.hpp (types and constants)
-NOT_INCLUDED = {"mg_launch.hip": ("mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE,
+_EIG = ("mg_eig_kernels.hpp", "mg_eig_dense.hpp", "mghip_eig.h")      # only mg_eig.hip includes these
+_HOST_UNIT = ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG    # mg_kernels.hpp comes with mg_host.hpp (types and constants)
+NOT_INCLUDED = {"mg_launch.hip": ("mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG,
                 "mg_engine.hip": _HOST_UNIT, "mg_solve.hip": _HOST_UNIT, "mg_dev.hip": _HOST_UNIT,
-                "mg_tail.hip": ("mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE,
-                "mg_pcg.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_heat_kernels.hpp") + _LINE,
-                "mg_heat.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp") + _LINE,
-                "mg_line.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp"),
+                "mg_tail.hip": ("mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG,
+                "mg_pcg.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG,
+                "mg_heat.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp") + _LINE + _EIG,
+                "mg_line.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _EIG,
+                "mg_eig.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE,
                 "mg_plan.hip": ("mg_kernels.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp",
-                                "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp", "mghip_heat.h") + _LINE}
+                                "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp", "mghip_heat.h") + _LINE + _EIG}
 # -ffp-contract=off: the kernels reproduce the reference's rounding sequence (no FMA contraction).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

@@ -58,6 +58,12 @@ class MgPcgStats(C.Structure):
                 ("true_residual", C.c_double), ("iterations", C.c_int32), ("status", C.c_int32)]
 
 
+class MgEigStats(C.Structure):
+    """mg_eig_stats (include/mghip_eig.h)"""
+    _fields_ = [("solve_seconds", C.c_double), ("precond_seconds", C.c_double), ("iterations", C.c_int32),
+                ("restarts", C.c_int32), ("status", C.c_int32)]
+
+
 class MgHeatStepInfo(C.Structure):
     """mg_heat_step_info (include/mghip.h, "Time stepping")"""
     _fields_ = [("lambda", C.c_double), ("rhs_norm", C.c_double), ("initial_residual", C.c_double),
@@ -199,6 +205,21 @@ LINE_SIGNATURES = {
     "mg_line_time_sweep": (_i, [_vp, _i, _pd]),
 }
 
+# name -> (restype, argtypes); every symbol include/mghip_eig.h declares (the block eigensolver)
+EIG_SIGNATURES = {
+    "mg_eig_create": (_i, [C.POINTER(MgConfig), _i, _i, C.POINTER(_vp)]),
+    "mg_eig_destroy": (_i, [_vp]),
+    "mg_eig_last_error": (C.c_char_p, [_vp]),
+    "mg_eig_set_coefficient": (_i, [_vp, _vp, _i]),
+    "mg_eig_solve": (_i, [_vp, _i, _vp, _i, _d, _i, _pd, _vp, _pd, _pd, _i, _pi, _pi, C.POINTER(MgEigStats)]),
+    "mg_eig_host_ritz": (_i, [_i, _i, _pd, _pd, _pd, _pd]),
+    "mg_dev_eig_apply": (_i, [_i] * 4 + [C.c_int64] + [_d] * 3 + [_vp] * 4),
+    "mg_dev_eig_gram": (_i, [_i] * 3 + [C.c_int64, _i, _vp, _i] + [_vp] * 4),
+    "mg_dev_eig_combine": (_i, [_i] * 3 + [C.c_int64, _i, _vp, _i] + [_vp] * 3),
+    "mg_dev_eig_residual": (_i, [_i] * 4 + [C.c_int64] + [_vp] * 7),
+    "mg_eig_time_op": (_i, [_vp, _i, _i, _pd]),
+}
+
 _lib = None
 
 
@@ -244,7 +265,8 @@ def load():
                           "mixed_precision_multigrid_solvers_for_pdes_amd._build`")
     _share_torch_hip_runtime()
     lib = C.CDLL(path)
-    for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()) + \
+            list(EIG_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib
