@@ -220,6 +220,16 @@ EIG_SIGNATURES = {
     "mg_eig_time_op": (_i, [_vp, _i, _i, _pd]),
 }
 
+# name -> (restype, argtypes); every symbol include/mghip_ho.h declares (the fourth-order compact scheme of the Krylov loop)
+HO_SIGNATURES = {
+    "mg_pcg_set_order": (_i, [_vp, _i]),
+    "mg_dev_ho_direction": (_i, [_i] * 3 + [_d] * 4 + [_vp] * 8),
+    "mg_dev_ho_residual": (_i, [_i] * 3 + [_d] * 4 + [_vp] * 6),
+    "mg_dev_ho_rhs": (_i, [_i] * 3 + [_vp] * 3),
+    "mg_op_apply_ho": (_i, [_i] * 2 + [_d] * 4 + [_vp] * 2),
+    "mg_op_rhs_ho": (_i, [_i] * 2 + [_vp] * 2),
+}
+
 _lib = None
 
 
@@ -266,7 +276,7 @@ def load():
     _share_torch_hip_runtime()
     lib = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()) + \
-            list(EIG_SIGNATURES.items()):
+            list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -232,6 +232,17 @@ void line_plan_free(mg_line_plan* p);
 int line_plan_set_sigma(mg_line_plan* p, double sigma, std::string* err);
 void d_line_colour(const mg_line_plan* p, int colour, double omega, void* u, const void* rhs, hipStream_t st);
 
+// mg_ho.hip: the fourth-order compact nine-point operator A4 and its right-hand side average R (mg_ho_kernels.hpp;
+// include/mghip_ho.h), fp64 fields with pitch ld, constant coefficients.  An int result is the number of partials written.
+//   direction: p_out = z + beta p_in (beta NULL: z), q = A4 p_out, partials of p_out . q   (pcg_direction_kernel's contract)
+//   residual:  r = g - A4 x on interior cells, 0 on the ring (r NULL: not stored), partials of the sum of r^2
+//   rhs:       g = R f on interior cells, the ring of f on the ring
+int d_ho_direction(const double* z, const double* p_in, double* p_out, double* q, const double* beta, double* partials, int nx,
+                   int ny, int ld, double hx, double hy, double coeff, double sigma, hipStream_t st);
+int d_ho_residual(const double* x, const double* g, double* r, double* partials, int nx, int ny, int ld, double hx, double hy,
+                  double coeff, double sigma, hipStream_t st);
+void d_ho_rhs(const double* f, double* g, int nx, int ny, int ld, hipStream_t st);
+
 // mg_engine.hip: what the solve loop (mg_solve.hip) and the stateless ABI (mg_dev.hip) use of the handle and cycle driver.
 // hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which a
 // hipStreamNonBlocking stream does not wait for: alloc_zero zeroes on the stream that will use the memory.

@@ -9,8 +9,14 @@
 //
 // Everything up to alpha of iteration k + 1 writes only z, p, q and scalars, so with lookahead it is queued before the host waits
 // for the norm of iteration k (a solve that ends there synchronises and drops it): the device never idles on the host.
+//
+// Under mg_pcg_set_order(4) (include/mghip_ho.h) A is the compact nine-point operator A4 and f is replaced by g = R f, formed
+// once per solve; the kernels are those of mg_ho.hip (d_ho_*), everything else -- the five-point preconditioner included -- is
+// the same code.
 #include "mg_launch.hpp"
 #include "mg_pcg_kernels.hpp"
+
+#include "../../include/mghip_ho.h"
 
 #include <atomic>
 
@@ -42,6 +48,8 @@ struct mg_pcg {
   unsigned long long seq = 0;
   double sigma = 0.0;
   bool varcoef = false;
+  int order = 2;                        // 2: the five-point operator, 4: the compact nine-point scheme (mg_pcg_set_order)
+  double* g = nullptr;                  // order 4: R f of the current solve (allocated when order 4 is first set)
   bool eng_has_rhs = false;
   hipEvent_t ev[2 * kTimedIters] = {};
   int nev = 0;
@@ -110,7 +118,7 @@ int eng_rc(mg_pcg* s, int rc) {
 
 void release(mg_pcg* s) {
   if (s->eng) { (void)mg_destroy(s->eng); s->eng = nullptr; }
-  for (double** p : {&s->x, &s->r, &s->z, &s->q, &s->f, &s->a, &s->staging, &s->p[0], &s->p[1], &s->partials, &s->sc})
+  for (double** p : {&s->x, &s->r, &s->z, &s->q, &s->f, &s->a, &s->g, &s->staging, &s->p[0], &s->p[1], &s->partials, &s->sc})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
   if (s->h_sc) { (void)hipHostFree(s->h_sc); s->h_sc = nullptr; }
   if (s->mbox) { (void)hipHostFree(s->mbox); s->mbox = nullptr; }
@@ -158,9 +166,12 @@ int front(mg_pcg* s, int k) {
   launch_scalars(k == 0 ? mg::kPcgBeta0 : (flex ? mg::kPcgBetaFlex : mg::kPcgBetaFr), s->partials, nd, s->partials + s->np,
                  flex ? nd : 0, s->sc, nullptr, 0, st);
   const int nxt = s->cur ^ 1;
-  const int nq = launch_direction(s->z, k == 0 ? nullptr : s->p[s->cur], s->p[nxt], s->q, s->varcoef ? s->a : nullptr,
-                                  k == 0 ? nullptr : s->sc + mg::kPcgBeta, s->partials, s->nx, s->ny, s->ld, s->hx, s->hy,
-                                  s->cfg.coeff, s->sigma, st);
+  const double* p_old = k == 0 ? nullptr : s->p[s->cur];
+  const double* beta = k == 0 ? nullptr : s->sc + mg::kPcgBeta;
+  const int nq = s->order == 4
+      ? d_ho_direction(s->z, p_old, s->p[nxt], s->q, beta, s->partials, s->nx, s->ny, s->ld, s->hx, s->hy, s->cfg.coeff, s->sigma, st)
+      : launch_direction(s->z, p_old, s->p[nxt], s->q, s->varcoef ? s->a : nullptr, beta, s->partials, s->nx, s->ny, s->ld, s->hx,
+                         s->hy, s->cfg.coeff, s->sigma, st);
   s->cur = nxt;
   launch_scalars(mg::kPcgAlphaOp, s->partials, nq, nullptr, 0, s->sc, nullptr, 0, st);
   HIPC(&s->err, hipGetLastError());
@@ -207,19 +218,29 @@ int solve_resident(mg_pcg* s, double tol, int max_iter, double* hist, int hist_c
   hipStream_t st = s->eng->stream;
   const double t0 = now_s();
   const int nx = s->nx, ny = s->ny, ld = s->ld;
-  // sum of f^2 over the ring (r = f there in the project's norm), r = f - A x with a zero ring, sum of r^2
-  const int win[4][4] = {{0, 1, 0, ny}, {nx - 1, nx, 0, ny}, {1, nx - 1, 0, 1}, {1, nx - 1, ny - 1, ny}};
-  for (int k = 0; k < 4; ++k) {
-    const int n = d_sumsq(MG_F64, s->f, s->partials, ld, win[k][0], win[k][1], win[k][2], win[k][3], st);
-    launch_reduce(s->partials, n, s->sc + kRing0 + k, st);
-  }
-  if (s->varcoef) d_var(mg::kVarResidual, MG_F64, s->x, s->a, s->f, s->r, nx, ny, ld, s->hx, s->hy, 1.0, s->cfg.coeff, 0, 0, st, s->sigma);
-  else d_residual(MG_F64, s->x, s->f, s->r, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, false, s->sigma);
-  hipLaunchKernelGGL(mg::pcg_zero_ring_kernel, dim3(std::max(1, std::min(64, (2 * (nx + ny) + mg::kBlock - 1) / mg::kBlock))),
-                     dim3(mg::kBlock), 0, st, s->r, nx, ny, ld);
-  {
-    const int n = d_sumsq(MG_F64, s->r, s->partials, ld, 1, nx - 1, 1, ny - 1, st);
+  const bool ho = s->order == 4;
+  if (ho) {
+    // g = R f; r = g - A4 x with a zero ring and the sum of r^2 in one launch.  The ring of f is data of the scheme here and
+    // does not enter the norm: the four ring sums are zero
+    HIPC(&s->err, hipMemsetAsync(s->sc + kRing0, 0, 4 * sizeof(double), st));
+    d_ho_rhs(s->f, s->g, nx, ny, ld, st);
+    const int n = d_ho_residual(s->x, s->g, s->r, s->partials, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, s->sigma, st);
     launch_reduce(s->partials, n, s->sc + kRr0, st);
+  } else {
+    // sum of f^2 over the ring (r = f there in the project's norm), r = f - A x with a zero ring, sum of r^2
+    const int win[4][4] = {{0, 1, 0, ny}, {nx - 1, nx, 0, ny}, {1, nx - 1, 0, 1}, {1, nx - 1, ny - 1, ny}};
+    for (int k = 0; k < 4; ++k) {
+      const int n = d_sumsq(MG_F64, s->f, s->partials, ld, win[k][0], win[k][1], win[k][2], win[k][3], st);
+      launch_reduce(s->partials, n, s->sc + kRing0 + k, st);
+    }
+    if (s->varcoef) d_var(mg::kVarResidual, MG_F64, s->x, s->a, s->f, s->r, nx, ny, ld, s->hx, s->hy, 1.0, s->cfg.coeff, 0, 0, st, s->sigma);
+    else d_residual(MG_F64, s->x, s->f, s->r, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, false, s->sigma);
+    hipLaunchKernelGGL(mg::pcg_zero_ring_kernel, dim3(std::max(1, std::min(64, (2 * (nx + ny) + mg::kBlock - 1) / mg::kBlock))),
+                       dim3(mg::kBlock), 0, st, s->r, nx, ny, ld);
+    {
+      const int n = d_sumsq(MG_F64, s->r, s->partials, ld, 1, nx - 1, 1, ny - 1, st);
+      launch_reduce(s->partials, n, s->sc + kRr0, st);
+    }
   }
   HIPC(&s->err, hipGetLastError());
   HIPC(&s->err, hipMemcpyAsync(s->h_sc, s->sc + kRing0, 5 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -251,7 +272,8 @@ int solve_resident(mg_pcg* s, double tol, int max_iter, double* hist, int hist_c
   }
   if (rc != MG_OK) { (void)hipStreamSynchronize(st); return rc; }
   // the true residual of the returned iterate, by the engine's own residual-norm kernels (what mg_residual_norm computes)
-  const int nt = s->varcoef
+  const int nt = ho ? d_ho_residual(s->x, s->g, nullptr, s->partials, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, s->sigma, st)
+      : s->varcoef
       ? d_var_residual_norm(MG_F64, s->x, s->a, s->f, s->partials, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, s->sigma)
       : d_residual_norm(MG_F64, s->x, s->f, s->partials, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, false, s->sigma);
   launch_reduce(s->partials, nt, s->sc + kTrue, st);
@@ -363,6 +385,8 @@ int mg_pcg_set_lookahead(mg_pcg* s, int on) {
 
 int mg_pcg_set_coefficient(mg_pcg* s, const void* a_host_or_null, int host_dtype) {
   if (!s || !valid_dtype(host_dtype)) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_coefficient: bad argument");
+  if (a_host_or_null && s->order == 4)
+    return pfail(s, MG_ERR_STATE, "mg_pcg_set_coefficient: the fourth-order scheme needs constant coefficients (mg_pcg_set_order(2) first)");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   ENG(mg_set_coefficient(s->eng, a_host_or_null, host_dtype));
   if (!a_host_or_null) { s->varcoef = false; return MG_OK; }
@@ -370,6 +394,20 @@ int mg_pcg_set_coefficient(mg_pcg* s, const void* a_host_or_null, int host_dtype
   const int rc = upload(s, s->a, a_host_or_null, host_dtype);
   if (rc != MG_OK) return rc;
   s->varcoef = true;
+  return MG_OK;
+}
+
+int mg_pcg_set_order(mg_pcg* s, int order) {
+  if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_pcg_set_order: NULL solver");
+  if (order != 2 && order != 4) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_order: order must be 2 or 4");
+  if (order == 4 && s->varcoef)
+    return pfail(s, MG_ERR_STATE, "mg_pcg_set_order: the fourth-order scheme needs constant coefficients (mg_pcg_set_coefficient(NULL) first)");
+  if (order == 4 && !s->g) {
+    HIPC(&s->err, hipSetDevice(s->cfg.device));
+    const int rc = alloc_zero(&s->err, (void**)&s->g, field_bytes(s), s->eng->stream);
+    if (rc != MG_OK) return rc;
+  }
+  s->order = order;
   return MG_OK;
 }
 

@@ -50,6 +50,7 @@ class PCGEngine:
         _pcg_check(lib.mg_pcg_create(C.byref(cfg), int(num_cycles), -1 if flexible is None else int(bool(flexible)),
                                      C.byref(self._h)))
         self.flexible = bool(smoother != _lib.MG_JACOBI or pre != post) if flexible is None else bool(flexible)
+        self.order = 2
 
     def _check(self, rc):
         _pcg_check(rc, self._h)
@@ -84,6 +85,12 @@ class PCGEngine:
     def set_shift(self, sigma):
         self._check(self._lib.mg_pcg_set_shift(self._h, float(sigma)))
 
+    def set_order(self, order):
+        """2 (default): the five-point operator; 4: the fourth-order compact nine-point scheme (include/mghip_ho.h), constant
+        coefficients only.  The preconditioner is the five-point cycle either way."""
+        self._check(self._lib.mg_pcg_set_order(self._h, int(order)))
+        self.order = int(order)
+
     def set_lookahead(self, on):
         self._check(self._lib.mg_pcg_set_lookahead(self._h, int(bool(on))))
 
@@ -93,7 +100,7 @@ class PCGEngine:
         return {"iterations": n, "converged": bool(conv.value), "residual_history": h,
                 "final_residual": h[-1] if h else stats.initial_residual, "true_residual": stats.true_residual,
                 "initial_residual": stats.initial_residual, "status": _lib.PCG_STATUS.get(stats.status, stats.status),
-                "flexible": self.flexible, "solve_seconds": stats.solve_seconds, "precond_seconds": stats.precond_seconds}
+                "flexible": self.flexible, "order": self.order, "solve_seconds": stats.solve_seconds, "precond_seconds": stats.precond_seconds}
 
     def solve(self, rhs, u0=None, tol=1e-8, max_iterations=50):
         """host arrays in, host array out (the dtype of rhs: float32 or float64); the ring of u0 is the Dirichlet data"""
@@ -136,11 +143,16 @@ class PCGSolver:
     multigrid cycles, on the device.  Shaped like MultigridSolver: setup(fine_grid, operator, ...), solve(grid, operator, rhs).
 
     precision is the PRECONDITIONER's ("double", "single_managed", "mixed"); the outer loop is always fp64.  flexible=None
-    picks the flexible beta whenever the cycle is not symmetric (anything but Jacobi with pre == post)."""
+    picks the flexible beta whenever the cycle is not symmetric (anything but Jacobi with pre == post).
+
+    order=4 discretises -Laplacian (+ shift) with the fourth-order compact nine-point scheme (include/mghip_ho.h): the loop
+    solves A4 u = R f, preconditioned by the same five-point cycle.  The right-hand side is then read on its ring too (the
+    Dirichlet data is still the ring of the initial guess), the residual norms run over interior cells only, and the
+    operator must have constant coefficients."""
 
     def __init__(self, max_levels=4, max_iterations=50, tolerance=1e-8, cycle_type="V", pre_smooth_iterations=2,
                  post_smooth_iterations=2, num_cycles=1, flexible=None, precision="double", device_id=0,
-                 coarse_tolerance=1e-12, coarse_max_iterations=1000, coarse_direct=None):
+                 coarse_tolerance=1e-12, coarse_max_iterations=1000, coarse_direct=None, order=2):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(PRECISIONS)} (the preconditioner's; the Krylov loop is fp64), "
                              f"not {precision!r}")
@@ -149,6 +161,8 @@ class PCGSolver:
             raise ValueError(f"unknown cycle type {cycle_type!r}")
         if int(num_cycles) < 1:
             raise ValueError("num_cycles must be >= 1")
+        if order not in (2, 4):
+            raise ValueError(f"order must be 2 (five-point) or 4 (compact nine-point), not {order!r}")
         if int(max_iterations) < 1:
             raise ValueError("max_iterations must be >= 1")
         if pre_smooth_iterations < 0 or post_smooth_iterations < 0 or pre_smooth_iterations + post_smooth_iterations == 0:
@@ -160,6 +174,7 @@ class PCGSolver:
         self.num_cycles, self.flexible, self.precision = int(num_cycles), flexible, precision
         self.device_id = device_id
         self.coarse_tolerance, self.coarse_max_iterations, self.coarse_direct = coarse_tolerance, coarse_max_iterations, coarse_direct
+        self.order = int(order)
         self.grid = self.operator = self._engine = None
 
     def setup(self, fine_grid, operator, restriction_op=None, prolongation_op=None, smoother=None):
@@ -178,6 +193,9 @@ class PCGSolver:
         coeff = float(getattr(operator, "coefficient", -1.0))
         if not coeff < 0:
             raise ValueError("conjugate gradients need an SPD operator: coefficient < 0 (-Laplacian, -div(a grad .))")
+        if self.order == 4 and hasattr(operator, "field"):
+            raise NotImplementedError("order=4 (the compact nine-point scheme) needs constant coefficients: -Laplacian or "
+                                      "-Laplacian + shift, not a DiffusionOperator")
         field = operator.field(fine_grid) if hasattr(operator, "field") else None
         self.close()
         self.grid, self.operator = fine_grid, operator
@@ -187,6 +205,8 @@ class PCGSolver:
                                  self.flexible, self.device_id, coarse_direct=self.coarse_direct)
         if field is not None:
             self._engine.set_coefficient(field)
+        if self.order != 2:
+            self._engine.set_order(self.order)
 
     def solve(self, grid, operator, rhs, initial_guess=None):
         if self._engine is None or grid.shape != self.grid.shape:
