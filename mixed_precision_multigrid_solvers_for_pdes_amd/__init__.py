@@ -25,6 +25,7 @@ from .heat_device import DeviceHeatStepper
 from .applications import MultigridPreconditioner, PoissonSolver2D
 from .krylov import PCGEngine, PCGSolver
 from .eigen import EigenEngine, EigenSolver
+from .flow import VorticityStreamSolver
 
 __all__ = [
     "Grid", "BaseOperator", "LaplacianOperator", "DiffusionOperator", "HelmholtzOperator", "RestrictionOperator", "ProlongationOperator",
@@ -37,6 +38,6 @@ __all__ = [
     "MixedPrecisionMultigrid", "PoissonProblem", "default_max_levels",
     "PoissonSolver2D", "MultigridPreconditioner", "applications", "heat_equation", "HeatEquationSolver",
     "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver", "SeparableSource", "DeviceHeatStepper",
-    "EigenEngine", "EigenSolver",
+    "EigenEngine", "EigenSolver", "VorticityStreamSolver",
 ]
 __version__ = "0.1.0"

@@ -230,6 +230,39 @@ HO_SIGNATURES = {
     "mg_op_rhs_ho": (_i, [_i] * 2 + [_vp] * 2),
 }
 
+
+class MgFlowStepInfo(C.Structure):
+    """mg_flow_step_info (include/mghip_flow.h)"""
+    _fields_ = [("sigma", C.c_double), ("c0", C.c_double), ("c1", C.c_double), ("cfl", C.c_double), ("rhs_norm", C.c_double),
+                ("omega_initial_residual", C.c_double), ("omega_final_residual", C.c_double), ("psi_rhs_norm", C.c_double),
+                ("psi_initial_residual", C.c_double), ("psi_final_residual", C.c_double), ("omega_change", C.c_double),
+                ("seconds", C.c_double), ("omega_cycles", C.c_int32), ("psi_cycles", C.c_int32),
+                ("omega_converged", C.c_int32), ("psi_converged", C.c_int32)]
+
+
+MG_FLOW_FREE_SLIP, MG_FLOW_NO_SLIP = 0, 1
+MG_FLOW_OMEGA, MG_FLOW_PSI, MG_FLOW_N = 0, 1, 2
+
+# name -> (restype, argtypes); every symbol include/mghip_flow.h declares (the vorticity / stream-function stepper)
+FLOW_SIGNATURES = {
+    "mg_flow_create": (_i, [C.POINTER(MgConfig), _d, _i, C.POINTER(_vp)]),
+    "mg_flow_destroy": (_i, [_vp]),
+    "mg_flow_last_error": (C.c_char_p, [_vp]),
+    "mg_flow_set_walls": (_i, [_vp, _pd]),
+    "mg_flow_set_forcing": (_i, [_vp, _vp, _i]),
+    "mg_flow_set_state": (_i, [_vp, _vp, _i, _d, _i, C.POINTER(MgFlowStepInfo)]),
+    "mg_flow_get": (_i, [_vp, _i, _vp, _i]),
+    "mg_flow_get_device": (_i, [_vp, _i, _vp, _i, _i]),
+    "mg_flow_set_device": (_i, [_vp, _i, _vp, _i, _i]),
+    "mg_flow_step": (_i, [_vp, _d, _d, _i, C.POINTER(MgFlowStepInfo)]),
+    "mg_flow_diagnostics": (_i, [_vp, _pd]),
+    "mg_flow_velocity_max": (_i, [_vp, _pd]),
+    "mg_dev_flow_rhs": (_i, [_i] * 3 + [_d] * 6 + [_vp] * 9),
+    "mg_dev_flow_wall": (_i, [_i] * 3 + [_d] * 2 + [_i, _pd] + [_vp] * 3),
+    "mg_dev_flow_diag": (_i, [_i] * 3 + [_vp] * 5),
+    "mg_dev_flow_interior": (_i, [_i] * 3 + [_vp] * 6),
+}
+
 _lib = None
 
 
@@ -276,7 +309,7 @@ def load():
     _share_torch_hip_runtime()
     lib = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()) + \
-            list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()):
+            list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -1,0 +1,455 @@
+"""The device-resident vorticity / stream-function stepper (include/mghip_flow.h, csrc/mg_flow.hip) on a GPU: its kernels
+call by call against the NumPy restatement tests/flow_reference.py (bit for bit on dyadic unit-square grids), the discrete
+energy identity on the device's own Jacobian, steps with a fixed cycle count against the restatement's MGOracle solves, twenty
+lid-driven-cavity steps and the steady cavity through VorticityStreamSolver, the Adams-Bashforth start and a change of dt,
+and what a live stepper refuses."""
+import ctypes as C
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import mixed_precision_multigrid_solvers_for_pdes_amd as mg
+from mixed_precision_multigrid_solvers_for_pdes_amd import _lib
+from oracle import mg_oracle as O
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import flow_reference as R                                                        # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 2
+UNIT = (0.0, 1.0, 0.0, 1.0)
+KERNEL_CASES = [((5, 5), UNIT), ((9, 130), UNIT), ((65, 129), UNIT), ((257, 131), UNIT), ((21, 13), (0.0, 1.5, -0.2, 0.5))]
+CASE_IDS = ["%dx%d" % c[0] for c in KERNEL_CASES]
+SPEEDS = (0.75, -1.25, 0.5, 1.5)          # left v, right v, bottom u, top u: four distinct wall speeds
+
+
+def rel(a, b):
+    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _lib_pitch(ny):
+    ld = C.c_int(0)
+    _lib.check(_lib.load().mg_pitch_elems(_lib.MG_F64, ny, C.byref(ld)))
+    return ld.value
+
+
+class Field:
+    """an (nx, ny) fp64 device field with pitch ld between NaN guard rows; the pad columns hold NaN as well (the canary)"""
+
+    def __init__(self, arr, ld):
+        nx, ny = arr.shape
+        host = np.full((nx + 2 * GUARD, ld), np.nan)
+        host[GUARD:GUARD + nx, :ny] = arr
+        self.nx, self.ny, self.ld = nx, ny, ld
+        self.t = _torch().from_numpy(host).cuda()
+        self.start = host.copy()
+        self.ptr = C.c_void_p(self.t[GUARD:].data_ptr())
+
+    def numpy(self):
+        return self.t.cpu().numpy()
+
+    def field(self):
+        return self.numpy()[GUARD:GUARD + self.nx, :self.ny]
+
+    def outside_untouched(self, first_free_col):
+        """guard rows and the columns >= first_free_col still hold their bits"""
+        now, start = self.numpy().view(np.uint64), self.start.view(np.uint64)
+        mask = np.ones(now.shape, dtype=bool)
+        mask[GUARD:GUARD + self.nx, :first_free_col] = False
+        return bool(np.all(now[mask] == start[mask]))
+
+
+def _scalars(n):
+    return _torch().full((n,), float("nan"), dtype=_torch().float64, device="cuda")
+
+
+def _scratch(nx, ny):
+    n = C.c_int64(0)
+    _lib.check(_lib.load().mg_dev_scratch_bytes(nx, ny, C.byref(n)))
+    return _torch().full((n.value // 8,), float("nan"), dtype=_torch().float64, device="cuda")
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _dyadic(shape, domain):
+    """unit square with nx - 1 and ny - 1 powers of two: spacings and their reciprocal squares are exact"""
+    return domain == UNIT and all((n - 1) & (n - 2) == 0 for n in shape)
+
+
+# ======================================================================================================================
+# 1. the kernels, call by call
+# ======================================================================================================================
+@pytest.mark.parametrize("with_force", [False, True], ids=["noforce", "force"])
+@pytest.mark.parametrize("with_prev", [False, True], ids=["first", "ab2"])
+@pytest.mark.parametrize("shape,domain", KERNEL_CASES, ids=CASE_IDS)
+def test_rhs_kernel_equals_restatement(shape, domain, with_prev, with_force):
+    """f, N and the velocity maximum.  N and the maximum repeat the restatement's operations one by one (a true division by
+    12.0*hx*hy included), so they agree bit for bit on EVERY grid; f holds lap, which the kernels form with reciprocal
+    spacings where the oracle divides: bit for bit where those are exact (dyadic unit square), elsewhere within 4 x the
+    distance between the restatement and its own evaluation in another association (measured ~2e-16 of max |f| on the 21 x 13
+    grid: DESIGN.md 5.4)."""
+    lib = _lib.load()
+    nx, ny = shape
+    hx, hy = O.grid_spacing(nx, ny, domain)
+    ld = _lib_pitch(ny) + 4
+    rng = np.random.default_rng(nx * 1000 + ny + 2 * with_prev + with_force)
+    psi, w, Np, F = (rng.standard_normal(shape) for _ in range(4))          # non-zero rings everywhere
+    nu, dt, c0, c1 = 0.02, 0.01, 1.25, -0.25
+    args = (psi, w, nu, dt, hx, hy, c0, c1, Np if with_prev else None, F if with_force else None)
+    want_f, want_n, want_ss, want_m = R.rhs(*args)
+    runs = []
+    for _ in range(2):
+        fp, fw, fn, ff = Field(psi, ld), Field(w, ld), Field(Np, ld), Field(F, ld)
+        fo, no = Field(np.full(shape, np.nan), ld), Field(np.full(shape, np.nan), ld)
+        out2, scratch = _scalars(2), _scratch(nx, ny)
+        _lib.check(lib.mg_dev_flow_rhs(nx, ny, ld, hx, hy, nu, dt, c0, c1, fp.ptr, fw.ptr, fn.ptr if with_prev else None,
+                                       ff.ptr if with_force else None, fo.ptr, no.ptr, _p(scratch), _p(out2), None))
+        _torch().cuda.synchronize()
+        for o in (fo, no):
+            assert o.outside_untouched((ny + 1) // 2 * 2)              # nothing beyond roundup(ny, 2), nothing outside the nx rows
+        for f in (fp, fw, fn, ff):
+            assert f.outside_untouched(0)                              # the inputs keep every bit
+        if ny % 2:
+            assert not fo.numpy()[GUARD:GUARD + nx, ny].any() and not no.numpy()[GUARD:GUARD + nx, ny].any()      # the pad column: 0
+        runs.append((fo.field().copy(), no.field().copy(), out2.cpu().numpy().copy()))
+    got_f, got_n, (got_ss, got_m) = runs[0]
+    np.testing.assert_array_equal(got_n, want_n)
+    assert got_m == want_m
+    if _dyadic(shape, domain):
+        np.testing.assert_array_equal(got_f, want_f)
+    else:
+        spread = float(np.max(np.abs(R.rhs_other_association(*args) - want_f)))
+        print("spread of the restatement", spread / np.max(np.abs(want_f)), "device", rel(got_f, want_f))
+        assert 0.0 < spread < 1e-14 * np.max(np.abs(want_f))
+        assert np.max(np.abs(got_f - want_f)) <= 4 * spread
+    for a in (got_f, got_n):
+        for ring in (a[0, :], a[-1, :], a[:, 0], a[:, -1]):
+            assert not ring.any()
+    np.testing.assert_allclose(got_ss, np.sum(got_f * got_f), rtol=1e-13)
+    np.testing.assert_allclose(got_ss, want_ss, rtol=1e-13)
+    for a, b in zip(runs[0], runs[1]):
+        assert a.tobytes() == b.tobytes()                              # the same bits on every run
+
+
+def test_rhs_kernel_without_scalars_and_on_a_stream():
+    lib = _lib.load()
+    nx, ny = 37, 70
+    ld = _lib_pitch(ny)
+    rng = np.random.default_rng(9)
+    psi, w = rng.standard_normal((nx, ny)), rng.standard_normal((nx, ny))
+    fp, fw, fo, no = Field(psi, ld), Field(w, ld), Field(np.full((nx, ny), np.nan), ld), Field(np.full((nx, ny), np.nan), ld)
+    scratch = _scratch(nx, ny)
+    st = _torch().cuda.Stream()
+    with _torch().cuda.stream(st):
+        _lib.check(lib.mg_dev_flow_rhs(nx, ny, ld, 1 / 36, 1 / 69, 0.05, 0.02, 1.0, 0.0, fp.ptr, fw.ptr, None, None, fo.ptr, no.ptr,
+                                       _p(scratch), None, C.c_void_p(st.cuda_stream)))
+    st.synchronize()
+    want_f, want_n, _, _ = R.rhs(psi, w, 0.05, 0.02, 1 / 36, 1 / 69)
+    np.testing.assert_array_equal(no.field(), want_n)
+    assert rel(fo.field(), want_f) < 1e-13
+
+
+@pytest.mark.parametrize("kind", [R.FREE_SLIP, R.NO_SLIP], ids=["free_slip", "no_slip"])
+@pytest.mark.parametrize("shape,domain", KERNEL_CASES + [((3, 3), UNIT)], ids=CASE_IDS + ["3x3"])
+def test_wall_kernel_equals_restatement_bit_for_bit(shape, domain, kind):
+    """the same operations in the same order, divisions included: the same bits on every grid"""
+    lib = _lib.load()
+    nx, ny = shape
+    hx, hy = O.grid_spacing(nx, ny, domain)
+    ld = _lib_pitch(ny) + 4
+    rng = np.random.default_rng(nx + 7 * ny + kind)
+    psi, w = rng.standard_normal(shape), rng.standard_normal(shape)
+    fp, fw = Field(psi, ld), Field(w, ld)
+    _lib.check(lib.mg_dev_flow_wall(nx, ny, ld, hx, hy, kind, (C.c_double * 4)(*SPEEDS), fp.ptr, fw.ptr, None))
+    _torch().cuda.synchronize()
+    got = fw.field()
+    want = R.wall(w.copy(), psi, hx, hy, kind, SPEEDS)
+    np.testing.assert_array_equal(got, want)
+    np.testing.assert_array_equal(got[1:-1, 1:-1], w[1:-1, 1:-1])                   # the interior is untouched
+    if kind == R.NO_SLIP:                                                         # corners carry bottom and top
+        assert got[0, 0] == (2.0 * (psi[0, 0] - psi[0, 1])) / (hy * hy) + (2.0 * SPEEDS[2]) / hy
+        assert got[-1, -1] == (2.0 * (psi[-1, -1] - psi[-1, -2])) / (hy * hy) - (2.0 * SPEEDS[3]) / hy
+    assert fw.outside_untouched(ny) and fp.outside_untouched(0)
+
+
+@pytest.mark.parametrize("shape,domain", KERNEL_CASES, ids=CASE_IDS)
+def test_diag_and_interior_kernels(shape, domain):
+    lib = _lib.load()
+    nx, ny = shape
+    ld = _lib_pitch(ny) + 4
+    rng = np.random.default_rng(3 * nx + ny)
+    psi, w, old = (rng.standard_normal(shape) for _ in range(3))
+    fp, fw, fold = Field(psi, ld), Field(w, ld), Field(old, ld)
+    out3, scratch = _scalars(3), _scratch(nx, ny)
+    vals = []
+    for _ in range(2):
+        _lib.check(lib.mg_dev_flow_diag(nx, ny, ld, fp.ptr, fw.ptr, _p(scratch), _p(out3), None))
+        _torch().cuda.synchronize()
+        vals.append(out3.cpu().numpy().copy())
+    e, z, m = R.diag(psi, w)
+    scale = float(np.sum(np.abs(psi[1:-1, 1:-1] * w[1:-1, 1:-1])))
+    assert abs(vals[0][0] - e) <= 1e-13 * scale                       # a sum of both signs: relative to the sum of magnitudes
+    np.testing.assert_allclose(vals[0][1], z, rtol=1e-13)
+    assert vals[0][2] == m and vals[0].tobytes() == vals[1].tobytes()
+    for with_old in (False, True):
+        fo, out2 = Field(np.full(shape, np.nan), ld), _scalars(2)
+        _lib.check(lib.mg_dev_flow_interior(nx, ny, ld, fw.ptr, fold.ptr if with_old else None, fo.ptr, _p(scratch), _p(out2), None))
+        _torch().cuda.synchronize()
+        np.testing.assert_array_equal(fo.field(), R.interior(w))
+        assert fo.outside_untouched((ny + 1) // 2 * 2)
+        ss, mx = out2.cpu().numpy()
+        np.testing.assert_allclose(ss, np.sum(R.interior(w) ** 2), rtol=1e-13)
+        assert mx == (float(np.max(np.abs(w - old))) if with_old else 0.0)
+    assert fp.outside_untouched(0) and fw.outside_untouched(0) and fold.outside_untouched(0)
+
+
+# ======================================================================================================================
+# 2. conservation on the device
+# ======================================================================================================================
+@pytest.mark.parametrize("shape,domain", [((9, 9), UNIT), ((65, 129), UNIT), ((12, 7), (0.0, 1.5, -0.2, 0.5))], ids=["9x9", "65x129", "12x7"])
+def test_device_jacobian_conserves_energy_and_enstrophy(shape, domain):
+    lib = _lib.load()
+    nx, ny = shape
+    hx, hy = O.grid_spacing(nx, ny, domain)
+    ld = _lib_pitch(ny)
+    rng = np.random.default_rng(nx * ny)
+    psi = R.interior(rng.standard_normal(shape))
+    for w in (rng.standard_normal(shape), R.interior(rng.standard_normal(shape))):
+        fp, fw, fo, no = Field(psi, ld), Field(w, ld), Field(np.full(shape, np.nan), ld), Field(np.full(shape, np.nan), ld)
+        _lib.check(lib.mg_dev_flow_rhs(nx, ny, ld, hx, hy, 0.01, 0.01, 1.0, 0.0, fp.ptr, fw.ptr, None, None, fo.ptr, no.ptr,
+                                       _p(_scratch(nx, ny)), None, None))
+        _torch().cuda.synchronize()
+        J = no.field()
+        assert abs(math.fsum((psi * J).ravel())) <= 1e-13 * math.fsum(np.abs(psi * J).ravel())
+        if not w[0, :].any():                                         # the ring of w is zero too: enstrophy
+            assert abs(math.fsum((w * J).ravel())) <= 1e-13 * math.fsum(np.abs(w * J).ravel())
+        assert np.abs(J).max() > 0
+
+
+# ======================================================================================================================
+# 3. steps against the restatement, fixed cycle count (no stopping decision enters)
+# ======================================================================================================================
+def _smooth_state(shape, rng):
+    nx, ny = shape
+    x, y = np.linspace(0, 1, nx), np.linspace(0, 1, ny)
+    w0 = 5.0 * np.sin(np.pi * x[:, None]) * np.sin(2 * np.pi * y[None, :]) + 0.05 * rng.standard_normal(shape)
+    F = np.cos(np.pi * x[:, None]) * np.sin(np.pi * y[None, :]) + 0.05 * rng.standard_normal(shape)
+    return w0, F
+
+
+def _compare_step(info, winfo, key):
+    assert info["sigma"] == winfo["sigma"] and info["c0"] == winfo["c0"] and info["c1"] == winfo["c1"], key
+    np.testing.assert_allclose(info["cfl"], winfo["cfl"], rtol=1e-9, err_msg=str(key))
+    np.testing.assert_allclose(info["rhs_norm"], winfo["rhs_norm"], rtol=1e-9, err_msg=str(key))
+    np.testing.assert_allclose(info["final_residual"], winfo["omega"]["final_residual"], rtol=1e-9, err_msg=str(key))
+    np.testing.assert_allclose(info["psi_final_residual"], winfo["psi"]["final_residual"], rtol=1e-9, err_msg=str(key))
+
+
+@pytest.mark.parametrize("smoother,omega", [("jacobi", 0.8), ("rbgs", 1.0)])
+@pytest.mark.parametrize("shape", [(33, 33), (65, 129)], ids=lambda s: "%dx%d" % s)
+def test_steps_equal_restatement_with_a_fixed_cycle_count(shape, smoother, omega):
+    """tol = 0, max_cycles = 3: w and psi equal the restatement's step run with the pinned oracle's cycle, to the 1e-12 the
+    heat stepper's steps are held to in the same comparison (tests/test_gpu_heat_device.py).  The first step has no history;
+    the second halves dt (c0 = 1.25, c1 = -0.25); the third doubles it (c0 = 2, c1 = -1)."""
+    nx, ny = shape
+    w0, F = _smooth_state(shape, np.random.default_rng(nx + ny))
+    dt = 0.5 / (nx - 1)
+    ref = R.Flow(nx, ny, 0.02, R.NO_SLIP, SPEEDS, force=F, solver=R.CycleSolver(nx, ny, tol=0.0, max_cycles=3, smoother=smoother, omega=omega))
+    with mg.VorticityStreamSolver(mg.Grid(nx, ny), 0.02, "no_slip", dict(zip(("left", "right", "bottom", "top"), SPEEDS)), forcing=F,
+                                  tolerance=0.0, max_cycles=3, smoother=smoother, omega=omega, max_levels=32) as s:
+        first = s.set_vorticity(w0)
+        ref.set_state(w0)
+        assert first["psi_cycles"] == 3 and not first["psi_converged"]
+        assert rel(s.stream_function, ref.psi) <= 1e-12 and rel(s.vorticity, ref.w) <= 1e-12
+        for k, (step, c) in enumerate(((dt, (1.0, 0.0)), (dt / 2, (1.25, -0.25)), (dt, (2.0, -1.0)))):
+            info = s.step(step)
+            winfo = ref.step(step)
+            assert (info["c0"], info["c1"]) == c, k
+            assert rel(s.vorticity, ref.w) <= 1e-12, k
+            assert rel(s.stream_function, ref.psi) <= 1e-12, k
+            assert info["cycles"] == 3 and info["psi_cycles"] == 3 and not info["converged"], k
+            _compare_step(info, winfo, k)
+            np.testing.assert_allclose(info["omega_change"], winfo["omega_change"], rtol=1e-9)
+        e, z, m = R.diag(s.stream_function, s.vorticity)
+        d = s.diagnostics()
+        np.testing.assert_allclose([d["kinetic_energy"], d["enstrophy"]], [0.5 * s.hx * s.hy * e, 0.5 * s.hx * s.hy * z], rtol=1e-12)
+        assert s.velocity_max() == m
+        u, v = s.velocity()
+        psi = s.stream_function
+        np.testing.assert_array_equal(u[1:-1, 1:-1], (psi[1:-1, 2:] - psi[1:-1, :-2]) / (2 * s.hy))
+        np.testing.assert_array_equal(v[1:-1, 1:-1], -(psi[2:, 1:-1] - psi[:-2, 1:-1]) / (2 * s.hx))
+        assert (u[:, -1] == SPEEDS[3]).all() and (v[0, :] == SPEEDS[0]).all()
+        assert not psi[0, :].any() and not psi[-1, :].any() and not psi[:, 0].any() and not psi[:, -1].any()
+
+
+# ======================================================================================================================
+# 4. the lid-driven cavity at 33^2, Re = 100, dt = h/2
+# ======================================================================================================================
+TOL = 1e-10
+# Two runs of the restatement, solves to 1e-10 and to 1e-12, differ after 20 steps by 3.3e-11 of max |w| and 8.4e-11 of
+# max |psi| (and 2.5e-11 in the CFL numbers): where a stopping decision falls on the other side, that is how far the device
+# can be from the restatement.  The margin is ten solve tolerances.
+MARGIN = 10 * TOL
+
+
+def _cavity(n, **kw):
+    return mg.VorticityStreamSolver(mg.Grid(n, n), 0.01, "no_slip", {"top": 1.0}, tolerance=TOL, max_cycles=50, **kw)
+
+
+def test_twenty_cavity_steps_equal_the_restatement():
+    n = 33
+    dt = 0.5 / (n - 1)
+    ref = R.Flow(n, n, 0.01, R.NO_SLIP, (0.0, 0.0, 0.0, 1.0), solver=R.CycleSolver(n, n, tol=TOL))
+    ref.set_state(np.zeros((n, n)))
+    with _cavity(n) as s:
+        before = (s.uploads, s.downloads)
+        for k in range(20):
+            info, winfo = s.step(dt), ref.step(dt)
+            assert info["converged"] and info["omega_converged"] and info["psi_converged"], k
+            assert abs(info["cfl"] - winfo["cfl"]) <= MARGIN, k
+            assert info["lambda"] == winfo["sigma"] == 2.0 / (0.01 * dt)
+        assert (s.uploads, s.downloads) == before                      # no field crossed to the host
+        w, psi = s.vorticity, s.stream_function
+        print("20 steps: rel w", rel(w, ref.w), "rel psi", rel(psi, ref.psi))
+        assert rel(w, ref.w) <= MARGIN and rel(psi, ref.psi) <= MARGIN
+        # the prototype's figures
+        assert abs(R.psi_min(psi)[0] - (-0.0481294)) < 1e-6 and abs(np.max(np.abs(w[1:-1, 1:-1])) - 17.577) < 1e-3
+        assert s.steps == 20 and abs(s.time - 20 * dt) < 1e-12
+
+
+RATE_TOL = 3e-5          # max |w_new - w| / dt: reached after 1295 steps, T = 20.2
+
+
+@pytest.fixture(scope="module")
+def steady_reference():
+    """the restatement with direct solves to the same stopping rule (seconds on a CPU)"""
+    n = 33
+    dt = 0.5 / (n - 1)
+    ref = R.Flow(n, n, 0.01, R.NO_SLIP, (0.0, 0.0, 0.0, 1.0))
+    ref.set_state(np.zeros((n, n)))
+    steps = 0
+    while True:
+        steps += 1
+        if ref.step(dt)["omega_change"] / dt < RATE_TOL:
+            return ref, steps
+
+
+def test_steady_cavity_through_run_to_steady(steady_reference):
+    """psi_min and its place against the restatement run to the same rate with direct solves, which a converged multigrid
+    solve agrees with to the solve tolerance.  The march to the steady state contracts, so the solve errors of the steps do
+    not add up: the margin of the twenty-step test holds where both stop at the same step.  The restatement at this rate
+    (1295 steps) gives -0.10162145, 5.2e-8 from its own T = 20 value -0.1016214 (the rate there is 3.4e-5); the device is
+    held to that number to the 1e-6 the CPU run is.  Measured on an MI355X: 2 to 5 cycles per vorticity solve, 4 to 13 per
+    stream-function solve."""
+    ref, steps = steady_reference
+    n = 33
+    dt = 0.5 / (n - 1)
+    with _cavity(n) as s:
+        out = s.run_to_steady(dt, RATE_TOL, 4000)
+        print("steady: steps", out["steps"], "reference", steps, "omega cycles", min(out["omega_cycles"]), max(out["omega_cycles"]),
+              "psi cycles", min(out["psi_cycles"]), max(out["psi_cycles"]), "rate", out["rate"])
+        assert out["converged"] and out["all_solves_converged"] and out["rate"] < RATE_TOL
+        assert abs(out["steps"] - steps) <= 1
+        got, want = R.psi_min(s.stream_function), R.psi_min(ref.psi)
+        assert got[1:] == want[1:] == (0.625, 0.75)
+        assert abs(want[0] - (-0.1016214)) < 1e-7
+        if out["steps"] == steps:
+            assert abs(got[0] - want[0]) <= MARGIN
+        assert abs(got[0] - (-0.1016214)) < 1e-6
+        assert len(s.history) == out["steps"] and all(h[3] for h in s.history)
+
+
+# ======================================================================================================================
+# 5. the Adams-Bashforth start, a change of dt, advance
+# ======================================================================================================================
+def test_first_step_does_not_read_the_history_and_set_vorticity_clears_it():
+    n = 33
+    dt = 0.5 / (n - 1)
+    w0, F = _smooth_state((n, n), np.random.default_rng(5))
+    ld = _lib_pitch(n)
+    nan = _torch().full((n, ld), float("nan"), dtype=_torch().float64, device="cuda")
+    with mg.VorticityStreamSolver(mg.Grid(n, n), 0.02, "free_slip", forcing=F, tolerance=TOL) as s:
+        ref = R.Flow(n, n, 0.02, R.FREE_SLIP, force=F, solver=R.CycleSolver(n, n, tol=TOL))
+        for attempt in range(2):                   # fresh, then with the history of two steps behind it
+            s.set_device("N", nan)
+            s.set_vorticity(w0)
+            ref.set_state(w0)
+            info, winfo = s.step(dt), ref.step(dt)
+            assert (info["c0"], info["c1"]) == (1.0, 0.0), attempt
+            w, psi = s.vorticity, s.stream_function
+            assert np.isfinite(w).all() and np.isfinite(psi).all() and np.isfinite(s._get("N")).all()
+            assert rel(w, ref.w) <= MARGIN and rel(psi, ref.psi) <= MARGIN, attempt
+            info, winfo = s.step(dt / 4), ref.step(dt / 4)               # a change of dt: r = 1/4
+            assert (info["c0"], info["c1"]) == (1.125, -0.125) == (winfo["c0"], winfo["c1"])
+            assert rel(s.vorticity, ref.w) <= MARGIN and rel(s.stream_function, ref.psi) <= MARGIN, attempt
+        got = _torch().empty((n, ld), dtype=_torch().float64, device="cuda")
+        s.get_device("omega", got)
+        np.testing.assert_array_equal(got.cpu().numpy()[:, :n], s.vorticity)
+        assert not s.vorticity[0, :].any()                               # free slip: w = 0 on the walls
+
+
+def test_advance_picks_its_steps_from_the_device_maximum():
+    n = 33
+    h = 1.0 / (n - 1)
+    with _cavity(n) as s:
+        with pytest.raises(ValueError, match="at rest"):
+            s.advance(0.1)                                               # nothing moves yet: no CFL step to take
+        s.advance(4 * h, dt=h / 2)
+        assert s.steps == 8 and s.time == 4 * h
+        infos = s.advance(s.time + 0.3, cfl=0.4)
+        assert abs(s.time - (4 * h + 0.3)) < 1e-12 and len(infos) >= 2
+        for info in infos[:-1]:
+            np.testing.assert_allclose(info["cfl"], 0.4, rtol=1e-12)
+        assert 0.0 < infos[-1]["cfl"] <= 0.4 * (1 + 1e-12)
+        assert all(i["converged"] for i in infos)
+
+
+# ======================================================================================================================
+# 6. what a live stepper refuses, with no device work
+# ======================================================================================================================
+def test_live_stepper_refuses_bad_arguments():
+    n = 17
+    lib = _lib.load()
+    with _cavity(n) as s:
+        w_before = s.vorticity
+        buf = np.zeros((n, n))
+        for which in (-1, 3, 7):
+            assert lib.mg_flow_get(s._h, which, _lib.ptr(buf), _lib.MG_F64) == _lib.MG_ERR_INVALID_VALUE
+            assert b"mg_flow_get" in lib.mg_flow_last_error(s._h)
+            assert lib.mg_flow_get_device(s._h, which, _lib.ptr(buf), n + 1, _lib.MG_F64) == _lib.MG_ERR_INVALID_VALUE
+            assert lib.mg_flow_set_device(s._h, which, _lib.ptr(buf), n + 1, _lib.MG_F64) == _lib.MG_ERR_INVALID_VALUE
+        assert lib.mg_flow_get(s._h, 0, _lib.ptr(buf), 5) == _lib.MG_ERR_INVALID_VALUE
+        assert lib.mg_flow_get_device(s._h, 0, _lib.ptr(buf), n - 1, _lib.MG_F64) == _lib.MG_ERR_INVALID_VALUE       # pitch < ny
+        for bad in (np.nan, np.inf, -np.inf):
+            F = np.zeros((n, n))
+            F[3, 4] = bad
+            with pytest.raises(ValueError, match="finite"):
+                s.set_forcing(F)
+            with pytest.raises(ValueError, match="finite"):
+                s.set_vorticity(F)
+        with pytest.raises(ValueError, match="shape"):
+            s.set_forcing(np.zeros((n, n + 1)))
+        with pytest.raises(ValueError, match="finite"):
+            s.set_wall_speeds({"top": float("inf")})
+        for dt in (0.0, -0.1, float("nan"), float("inf")):
+            with pytest.raises(ValueError, match="dt"):
+                s.step(dt)
+        with pytest.raises(ValueError, match="max_cycles"):
+            s.step(0.01, max_cycles=0)
+        with pytest.raises(ValueError, match="tol"):
+            s.step(0.01, tol=float("nan"))
+        assert s.steps == 0 and s.vorticity.tobytes() == w_before.tobytes()           # the stepper is as it was
+        assert s.step(0.5 / (n - 1))["converged"]                                      # and no forcing was set: it still steps
+        assert np.isfinite(s.vorticity).all()
