@@ -416,7 +416,7 @@ int mg_comm_ranks(void* comm, int* nranks, int* rank);
  * -alpha (z.q) / (r.z)_old for a preconditioner that is not symmetric, < 0 auto: 1 exactly when cfg.smoother != MG_JACOBI or
  * pre != post.  The reported norm is sqrt(hx hy (sum of r^2 over interior cells + sum of f^2 over the ring)), what
  * mg_residual_norm gives for the same iterate; it is compared as norm < tol (absolute, like mg_iterate); hist[k] is the norm
- * after iteration k + 1.  A breakdown (p.Ap <= 0 or non-finite) ends the solve with status 2 and converged = 0; it is not an
+ * after iteration k + 1.  A breakdown (p.Ap <= 0 or non-finite, or r.z non-finite) ends the solve with status 2 and converged = 0; it is not an
  * error code, and the iterate returned is the last one before it.  All of the solver's work is queued on its engine's stream.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct mg_pcg mg_pcg;
@@ -456,7 +456,7 @@ const char* mg_pcg_last_error(const mg_pcg* s);
  *   scalars:   the one-workgroup kernel between them -- reduces partials_a[0, na) (and partials_b[0, nb)) in fixed order and
  *              advances a block of 10 doubles {rz, rz_old, zq, pq, alpha, beta, rr, flag, posted rr, posted flag}.  op 0: first dots
  *              (rz; clears the flag), 1: dots, beta = rz / rz_old, 2: dots, beta = -alpha zq / rz_old, 3: direction, alpha = rz / pq
- *              (pq <= 0 or non-finite: alpha = 0, flag = 1), 4: update, rr and the flag posted. */
+ *              (pq <= 0 or non-finite, or rz non-finite: alpha = 0, flag = 1), 4: update, rr and the flag posted. */
 int mg_dev_pcg_direction(int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, const double* a_or_null,
                          const double* z, const double* p_in_or_null, double* p_out, double* q, const double* beta_dev_or_null,
                          void* scratch, double* pq_dev, void* stream);

@@ -43,7 +43,9 @@ const char* mg_eig_last_error(const mg_eig* s);
 int mg_eig_set_coefficient(mg_eig* s, const void* a_host_or_null, int host_dtype);
 /* x0_host: (block_size, nx, ny) start vectors of host_dtype; vectors_out: (nev, nx, ny) of host_dtype, scaled to
  * hx hy sum v^2 = 1; eigenvalues and residuals: block_size doubles; hist: hist_cap doubles (max_iter + 1 are written at
- * most); n_iter: completed iterations. */
+ * most); n_iter: completed iterations.  Start vectors that are linearly dependent on the interior cells, or that hold a NaN
+ * or an Inf there (the Gram matrix of the block then has a non-finite row and cannot be factored), return
+ * MG_ERR_INVALID_VALUE before the first iteration; the solver stays usable. */
 int mg_eig_solve(mg_eig* s, int nev, const void* x0_host, int host_dtype, double tol, int max_iter, double* eigenvalues,
                  void* vectors_out, double* residuals, double* hist, int hist_cap, int* n_iter, int* converged,
                  mg_eig_stats* stats);

@@ -28,7 +28,15 @@
  * finite and > 0, wall_kind one of the two codes: anything else returns MG_ERR_INVALID_VALUE before any device work.  Each
  * solve stops at ||r|| < tol * max(1, ||f||_h); tol = 0 runs exactly max_cycles cycles (mg_heat's conventions).  Per step two
  * small readbacks (sum f^2 and the velocity maximum; sum w^2 and max |w_new - w|) plus mg_iterate's mailbox; no field crosses
- * to the host. */
+ * to the host.
+ *
+ * Special values.  Every maximum here (the velocity maximum m, max |w_new - w|) propagates NaN: it is NaN if any participating
+ * value is, otherwise the maximum, which may be +Inf; for finite fields it is fmax's value bit for bit.  The sums are plain
+ * IEEE sums of the participating cells (interior cells; ring, pad columns and rows outside the array never contribute).  A
+ * step on a state that holds a NaN or an Inf (mg_flow_set_device copies what it is given; a run can also blow up by itself)
+ * returns MG_OK: cfl, omega_change, the norms and the residuals of its info are non-finite wherever the restatement's are,
+ * tol * max(1, NaN) is tol, both solves run max_cycles cycles and report converged = 0.  The stepper stays usable:
+ * mg_flow_set_state with a finite field gives the steps of a fresh stepper. */
 #ifndef MGHIP_FLOW_H
 #define MGHIP_FLOW_H
 

@@ -182,6 +182,9 @@ int solve_on(mg_flow* s, mg_handle* eng, bool* has_rhs, const double* guess, dou
   if ((int)s->hist.size() < max_cycles) s->hist.resize(max_cycles);
   int n = 0, conv = 0;
   mg_stats stats;
+  // A NaN norm: std::max(1.0, NaN) is 1.0, so the target is `tol` and no NaN residual is below it -- the solve runs to its
+  // cap and reports converged = 0; the NaN itself is visible to the caller in rhs_norm.
+
   ENG(eng, mg_iterate(eng, tol * std::max(1.0, fnorm), max_cycles, s->hist.data(), max_cycles, &n, &conv, nullptr, &stats));
   ENG(eng, mg_get_solution_device(eng, dst, s->ld, MG_F64));
   *fnorm_out = fnorm;

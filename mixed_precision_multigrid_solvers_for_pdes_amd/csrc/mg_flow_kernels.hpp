@@ -22,9 +22,14 @@ struct FlowCoef {
   double d12;                // 12.0 * hx * hy
 };
 
+// The maximum that keeps a NaN: fmax returns the operand that is NOT one, which would report a field that has blown up as
+// a field at rest.  Every maximum of this file -- per thread, per wave, per block, flow_reduce_kernel -- is formed with
+// it, so the result is NaN if any participating value is; for other operands it is fmax's value, bit for bit.
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+
 __device__ __forceinline__ double wave_reduce_max(double x) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_down(x, o, 64));
+  for (int o = 32; o > 0; o >>= 1) x = nan_max(x, __shfl_down(x, o, 64));
   return x;
 }
 // Maximum over the block of NW waves; result valid in thread 0.  `red` is >= NW doubles of LDS of its own.
@@ -38,7 +43,7 @@ __device__ __forceinline__ double block_reduce_max(double x, double* red) {
   if (threadIdx.x == 0) {
     t = red[0];
 #pragma unroll
-    for (int w = 1; w < NW; ++w) t = fmax(t, red[w]);
+    for (int w = 1; w < NW; ++w) t = nan_max(t, red[w]);
   }
   return t;
 }
@@ -138,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void flow_rhs_kernel(const double* __restri
       of.v[e] = ov;
       on.v[e] = interior ? nn : 0.0;
       acc += ov * ov;
-      vmax = fmax(vmax, interior ? fabs(dpy) + fabs(dpx) : 0.0);
+      vmax = nan_max(vmax, interior ? fabs(dpy) + fabs(dpx) : 0.0);
     }
     if (gi < g.nx && gj0 < g.nyv) {
       stg(f_out + (size_t)gi * g.ld + gj0, of);
@@ -212,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void flow_interior_kernel(const double* __r
       const double ov = interior ? a.v[e] : 0.0;
       o.v[e] = ov;
       acc += ov * ov;
-      if (HAS_OLD) vmax = fmax(vmax, j + e < ny ? fabs(a.v[e] - b.v[e]) : 0.0);
+      if (HAS_OLD) vmax = nan_max(vmax, j + e < ny ? fabs(a.v[e] - b.v[e]) : 0.0);
     }
     stg(out + at, o);
   }
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(kBlock) void flow_diag_kernel(const double* __restr
         a1 += q.v[e] * q.v[e];
         const double pn = (e == N - 1) ? psi[at + N] : p.v[e + 1];
         const double ps = (e == 0) ? psi[at - 1] : p.v[e - 1];
-        vmax = fmax(vmax, fabs(pn - ps) + fabs(pe.v[e] - pw.v[e]));
+        vmax = nan_max(vmax, fabs(pn - ps) + fabs(pe.v[e] - pw.v[e]));
       }
     }
   }
@@ -270,7 +275,7 @@ __global__ __launch_bounds__(kReduceBlock) void flow_reduce_kernel(const double*
   double t;
   if ((max_mask >> blockIdx.x) & 1) {
     double m = 0.0;
-    for (int i = threadIdx.x; i < n; i += kReduceBlock) m = fmax(m, p[i]);
+    for (int i = threadIdx.x; i < n; i += kReduceBlock) m = nan_max(m, p[i]);
     t = block_reduce_max<kReduceBlock / 64>(m, red);
   } else {
     double a0 = 0.0, a1 = 0.0;

@@ -209,7 +209,7 @@ constexpr int kPcgRz = 0, kPcgRzOld = 1, kPcgZq = 2, kPcgPq = 3, kPcgAlpha = 4, 
 constexpr int kPcgBeta0 = 0;   // after the dots of the first iteration: rz only, the breakdown flag is cleared
 constexpr int kPcgBetaFr = 1;  // after the dots: beta = rz / rz_old (Fletcher-Reeves)
 constexpr int kPcgBetaFlex = 2;// after the dots: beta = -alpha (z . q) / rz_old (Polak-Ribiere, flexible)
-constexpr int kPcgAlphaOp = 3; // after the direction: alpha = rz / pq; pq <= 0 or non-finite sets the flag and alpha = 0
+constexpr int kPcgAlphaOp = 3; // after the direction: alpha = rz / pq; pq <= 0 or non-finite, or rz non-finite, sets the flag and alpha = 0
 constexpr int kPcgNormOp = 4;  // after the update: rr, posted with the flag to the mailbox
 
 struct PcgMailbox {
@@ -242,7 +242,8 @@ __global__ __launch_bounds__(kReduceBlock) void pcg_scalars_kernel(int op, const
     sc[kPcgRzOld] = old; sc[kPcgRz] = ta; sc[kPcgZq] = tb;
     sc[kPcgBeta] = (op == kPcgBetaFlex) ? -sc[kPcgAlpha] * tb / old : ta / old;
   } else if (op == kPcgAlphaOp) {
-    const bool bad = !(ta > 0.0) || !(ta <= 1.79769313486231570815e308);
+    // p . A p <= 0 or non-finite, or a non-finite r . z (alpha would be NaN or Inf with no flag raised)
+    const bool bad = !(ta > 0.0) || !(ta <= 1.79769313486231570815e308) || !(fabs(sc[kPcgRz]) <= 1.79769313486231570815e308);
     sc[kPcgPq] = ta;
     sc[kPcgAlpha] = bad ? 0.0 : sc[kPcgRz] / ta;
     if (bad) sc[kPcgFlag] = 1.0;

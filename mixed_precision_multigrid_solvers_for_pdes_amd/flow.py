@@ -55,7 +55,13 @@ class VorticityStreamSolver:
     (w = 0 on the walls).  forcing: F(x, y) on the grid, the curl of a body force (None: none).  tolerance / max_cycles:
     every solve stops at ||r|| < tolerance * max(1, ||f||_h).  The info dict of a step carries the heat stepper's keys for the
     vorticity solve (lambda = sigma = 2/(nu dt), rhs_norm, initial_residual, final_residual, cycles, converged,
-    solve_seconds) and psi_* for the stream-function solve, c0, c1, cfl and omega_change = max |w_new - w|."""
+    solve_seconds) and psi_* for the stream-function solve, c0, c1, cfl and omega_change = max |w_new - w|.
+
+    Non-finite states: the device maxima propagate NaN, so a step on a state that holds a NaN or an Inf still returns (MG_OK)
+    and its cfl, omega_change, norms and residuals are non-finite wherever the field is; no solve of such a step reports
+    convergence.  run_to_steady stops at the first step whose omega_change or cfl is not finite and returns converged False,
+    diverged True; advance(dt=None) raises FloatingPointError when the velocity maximum is not finite (ValueError when it
+    is 0: the fluid is at rest).  set_vorticity with a finite field makes the stepper usable again."""
 
     def __init__(self, grid, viscosity, wall="no_slip", wall_speeds=None, forcing=None, max_levels=None, tolerance=1e-10,
                  max_cycles=50, cycle="V", pre=2, post=2, smoother="jacobi", omega=0.8, coarse_tol=1e-12, coarse_maxit=1000,
@@ -207,6 +213,8 @@ class VorticityStreamSolver:
         while t_final - self.time > 1e-12 * max(1.0, abs(t_final)):
             if dt is None:
                 m = self.velocity_max()
+                if not np.isfinite(m):
+                    raise FloatingPointError(f"advance(dt=None): the velocity maximum is not finite ({m}): the state has blown up")
                 if not m > 0.0:
                     raise ValueError("advance(dt=None): the fluid is at rest (no velocity to take a CFL step from); give dt")
                 step = cfl * 2.0 * self.hx * self.hy / m
@@ -221,8 +229,9 @@ class VorticityStreamSolver:
 
     def run_to_steady(self, dt, rate_tol=1e-6, max_steps=100000):
         """Fixed-dt steps until max |w_new - w| / dt < rate_tol (taken on the device).  Returns steps, rate, converged,
-        all_solves_converged, omega_cycles and psi_cycles (lists)."""
-        rate, wc, pc, ok = float("inf"), [], [], True
+        diverged, all_solves_converged, omega_cycles and psi_cycles (lists).  The run stops at the first step whose
+        omega_change or cfl is not finite: diverged is True then and converged False."""
+        rate, wc, pc, ok, diverged = float("inf"), [], [], True, False
         n = 0
         while n < max_steps:
             info = self.step(dt)
@@ -230,10 +239,13 @@ class VorticityStreamSolver:
             wc.append(info["omega_cycles"]); pc.append(info["psi_cycles"])
             ok = ok and info["converged"]
             rate = info["omega_change"] / dt
+            if not (np.isfinite(info["omega_change"]) and np.isfinite(info["cfl"])):
+                diverged = True
+                break
             if rate < rate_tol:
                 break
-        return {"steps": n, "rate": rate, "converged": rate < rate_tol, "all_solves_converged": ok, "omega_cycles": wc,
-                "psi_cycles": pc, "time": self.time}
+        return {"steps": n, "rate": rate, "converged": (not diverged) and rate < rate_tol, "diverged": diverged,
+                "all_solves_converged": ok, "omega_cycles": wc, "psi_cycles": pc, "time": self.time}
 
     # ------------------------------------------------------------------ results
     @property

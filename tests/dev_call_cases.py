@@ -348,6 +348,94 @@ def _cases(seed, scale):
     return out
 
 
+# ---- finite extremes (tests/special_values.py, tests/test_gpu_range_edges.py): a list of its own -- the ids and seeds of
+# _cases are derived from list position and must not move
+SPECIAL_OP_SHAPES = {"f64": (35, 66), "f32": (34, 129)}      # one past the fp64 tile column (64) / at the fp32 one (128)
+SPECIAL_LEG_SHAPES = [(33, 130), (530, 513), (1102, 1122)]   # 8-row tiles, 16-row tiles, register-blocked
+SPECIAL_KINDS = ("tiny", "huge", "patches")
+
+
+def _special_case(out, entry, var, dt, dtc, comp, field, k):
+    """one case of `entry` with the dtypes given on the field kind `field`; k picks the leg family and the small choices"""
+    legs = ("down_leg", "up_leg", "span_leg")
+    if entry == "span_leg":
+        nx, ny = SPECIAL_LEG_SHAPES[2]
+    elif entry in legs:
+        nx, ny = SPECIAL_LEG_SHAPES[k % 3]
+    else:
+        nx, ny = SPECIAL_OP_SHAPES[dt or "f64"]
+    c = dict(entry=entry, disp="compare", nx=nx, ny=ny, pf=PITCHES[k % 3], field=field)
+    for key, val in (("dt", dt), ("dtc", dtc), ("comp", comp)):
+        if val is not None:
+            c[key] = val
+    if var:
+        c["var"] = True
+    sp = ("eq", "neq")[len(out) % 2]                      # dyadic spacings only
+    c["sp"] = sp
+    c["hx"], c["hy"], c["dyadic"] = SPACINGS[sp]
+    if entry == "jacobi":
+        c.update(omega=OMEGAS[k % 4])
+    elif entry == "rbgs_colour":
+        c.update(omega=OMEGAS[(k + 1) % 4], colour=k % 2, poff=(k // 2) % 2)
+    elif entry == "residual":
+        c.update(coeff=(-1.0, 0.37)[k % 2])
+    elif entry == "residual_mixed":
+        c.update(pc=PITCHES[(k + 1) % 3], coeff=(-1.0, 1.5)[k % 2])
+    elif entry == "sumsq":
+        c.update(window=((1, nx - 1, 3, ny - 2), (0, nx, 0, ny))[k % 2])
+    elif entry == "convert":
+        c.update(pc=PITCHES[(k + 1) % 3])
+    elif entry == "var_rdiag":
+        c.update(sigma=(0.0, 2.5)[k % 2])
+    elif entry in ("restrict", "prolong_add", "inject_ring"):
+        c.update(nxc=(nx + 1) // 2, nyc=(ny + 1) // 2, pc=PITCHES[(k + 1) % 3], sides=15, ci=0, cj=0)
+    elif entry in legs:
+        # the norm window of `patches` ends ahead of the large rectangle (rows from 0.62 nx), whose squares may be beyond fp64
+        win = (1, int(0.55 * nx), 1, ny - 1) if field == "patches" else (1, nx - 1, 1, ny - 1)
+        c.update(nxc=(nx + 1) // 2, nyc=(ny + 1) // 2, ci=0, cj=0, pc=PITCHES[(k + 1) % 3], sm=0 if entry == "span_leg" else k % 2,
+                 omega=OMEGAS[k % 4], poff=k % 2, coeff=-1.0, nsweep=2 - (k // 2) % 2, sides=15)
+        if entry == "down_leg":
+            c.update(zero_init=0, rect=None)
+        else:
+            c.update(window=win)
+        if entry == "span_leg":
+            c.update(nsweep_pre=1 + k % 2)
+    else:
+        raise KeyError(entry)
+    c["seed"] = 104729 * len(out) + 31
+    c["id"] = "%s%s-%s-%s-%dx%d-%s" % (entry, "_var" if var else "", field, "-".join(x for x in (dt, dtc, comp) if x), nx, ny, sp)
+    out.append(c)
+    return c
+
+
+def special_cases():
+    """one case per entry of ENTRIES, per dtype combination the default list has for that entry, per kind of finite extreme
+    field; then the convert, restrict and residual_mixed cases whose fp64 values straddle what fp32 holds ("straddle")"""
+    if "special" in _CACHE:
+        return _CACHE["special"]
+    combos = {}
+    for c in default_cases():
+        if c["disp"] == "compare" and c.get("tag") != "fuzz":
+            key = (c.get("dt"), c.get("dtc"), c.get("comp"))
+            lst = combos.setdefault(entry_name(c), [])
+            if key not in lst:
+                lst.append(key)
+    out = []
+    for name in ENTRIES:
+        var = name.endswith("_var")
+        entry = name[:-4] if var else name
+        for m, (dt, dtc, comp) in enumerate(combos[name]):
+            for n, field in enumerate(SPECIAL_KINDS):
+                _special_case(out, entry, var, dt, dtc, comp, field, m + n)
+    _special_case(out, "convert", False, "f64", "f32", None, "straddle", 0)
+    _special_case(out, "convert", False, "f32", "f64", None, "straddle", 1)
+    _special_case(out, "restrict", False, "f64", "f32", None, "straddle", 2)
+    _special_case(out, "restrict", False, "f64", "f64", None, "straddle", 3)
+    _special_case(out, "residual_mixed", False, "f32", "f64", None, "straddle", 4)
+    _CACHE["special"] = out
+    return out
+
+
 _CACHE = {}
 
 
@@ -449,15 +537,27 @@ SWEEP_OUTPUTS = {"jacobi": ["out"], "down_leg": ["out"], "up_leg": ["out"], "spa
 
 
 def build_arrays(case, device="cpu"):
+    """the arrays of a call.  case["field"] (optional; tests/special_values.py): a kind of FIELD_KINDS scales the seeded data of
+    every `in` / `inout` array by the scale of the narrowest dtype among the call's arrays, "straddle" writes fp64 values
+    around the ends of the fp32 range over part of it; coefficient fields stay as they are"""
     import torch
     rng = np.random.default_rng(case["seed"])
+    field = case.get("field")
+    if field:
+        import special_values as SV
+        narrow = SV.narrowest(case)
     A = {}
     for name, (dt, nx, ny, pk, role) in array_specs(case).items():
         ld = pitch(pk, dt, ny)
         host = sentinel(NPDT[dt], (nx + 2 * GUARD, ld))
         if role != "out":
             data = rng.standard_normal((nx, ny))
-            host[GUARD:GUARD + nx, :ny] = (np.exp(0.5 * data) if role == "coef" else data).astype(NPDT[dt])
+            if field and role != "coef":
+                data = SV.straddle_fill(data) if field == "straddle" else SV.apply_field(field, data, narrow)
+                with np.errstate(over="ignore", under="ignore"):
+                    host[GUARD:GUARD + nx, :ny] = data.astype(NPDT[dt])
+            else:
+                host[GUARD:GUARD + nx, :ny] = (np.exp(0.5 * data) if role == "coef" else data).astype(NPDT[dt])
         A[name] = Arr(torch, device, host, nx, ny, ld)
     return A
 
@@ -568,12 +668,14 @@ def _fail(case, name, bad, got, ref, what):
         entry_name(case), case["id"], name, what, len(idx), i, j, got[i, j], int(bits(got)[i, j]), ref[i, j], int(bits(ref)[i, j]), tile_of(case, i, j)))
 
 
-def compare_array(case, name, got_full, ref_full, nx, ny, exact=None, tol_dtype=None, far_edge_open=False):
+def compare_array(case, name, got_full, ref_full, nx, ny, exact=None, tol_dtype=None, far_edge_open=False, special=False):
     """one output, guards included.  Bit for bit on dyadic spacings (sentinels included: a cell the reference leaves untouched
     must still hold the sentinel), within tau otherwise; pad columns are exempt; guard rows must be untouched.
     tol_dtype: the dtype whose bound applies where it is not the array's own (the down leg's coarse rhs is rounded in the fine
     level's dtype and in its own: an fp64 array of fp32-rounded values, or an fp32 rounding of fp64 values that a last-bit
-    difference can flip)."""
+    difference can flip).
+    special (exact comparisons only): the data may hold non-finite values -- special_values.same_special: the cells that hold
+    the sentinel are the same, the NaN masks are identical and every other cell, infinities included, has equal bits."""
     sent = SENT_BITS[got_full.dtype.itemsize]
     gb = bits(got_full)
     guards = np.ones(gb.shape[0], dtype=bool)
@@ -593,7 +695,11 @@ def compare_array(case, name, got_full, ref_full, nx, ny, exact=None, tol_dtype=
         free &= (g == sent)
     exact = case["dyadic"] if exact is None else exact
     if exact:
-        bad = (g != r) & ~free
+        if special:
+            import special_values as SV
+            bad = (((g == sent) != (r == sent)) | SV.special_mismatch(got, ref)) & ~free
+        else:
+            bad = (g != r) & ~free
         if bad.any():
             _fail(case, name, bad, got, ref, "differs")
         return
@@ -609,11 +715,15 @@ def compare_array(case, name, got_full, ref_full, nx, ny, exact=None, tol_dtype=
         _fail(case, name, bad, got, ref, "differs by more than %.3g" % tau)
 
 
-def compare_sum(case, got, ref, n_w, w_max, field_dtype, exact=None):
+def compare_sum(case, got, ref, n_w, w_max, field_dtype, exact=None, special=False):
     """sums: relative 1e-12 on dyadic spacings (partial sums run over other tiles); otherwise the per-cell bound tau carried
     through the sum by Cauchy-Schwarz, |S - S_ref| <= 2 sqrt(S_ref n_w) tau + n_w tau^2, plus the same 1e-12 S_ref.  An empty
     window gives exactly 0.0."""
     exact = case["dyadic"] if exact is None else exact
+    if special and not (math.isfinite(got) and math.isfinite(ref)):      # NaN where the reference's is, the same infinity
+        import special_values as SV
+        assert SV.same_special(got, ref), "mg_dev_%s case %s: sum of squares %r, reference %r" % (entry_name(case), case["id"], got, ref)
+        return
     if n_w == 0:
         assert got == 0.0 and ref == 0.0, "mg_dev_%s case %s: sum over an empty window is %r (reference %r)" % (entry_name(case), case["id"], got, ref)
         return
@@ -625,8 +735,9 @@ def compare_sum(case, got, ref, n_w, w_max, field_dtype, exact=None):
         entry_name(case), case["id"], got, ref, abs(got - ref), bound, n_w)
 
 
-def compare_call(case, got, got_sum, ref, ref_sum, ref_ops, before=None):
-    """every output of one call against the reference; `before`: snapshot taken before the call (inputs must be unchanged)"""
+def compare_call(case, got, got_sum, ref, ref_sum, ref_ops, before=None, special=False):
+    """every output of one call against the reference; `before`: snapshot taken before the call (inputs must be unchanged);
+    special: by special_values.same_special (data that may hold non-finite values; dyadic spacings)"""
     e = case["entry"]
     specs = array_specs(case)
     exact = True if e in ("restrict", "inject_ring", "prolong_add", "convert", "sumsq") else None
@@ -634,11 +745,11 @@ def compare_call(case, got, got_sum, ref, ref_sum, ref_ops, before=None):
         dt, nx, ny, pk, role = specs[name]
         # the coarse rhs is rounded in the fine level's dtype and again in its own: the looser of the two bounds
         loose = np.dtype(np.float32) if name == "rhs_c" and "f32" in (case["dt"], case["dtc"]) else None
-        compare_array(case, name, got[name], ref[name], nx, ny, exact, loose, name in SWEEP_OUTPUTS.get(e, ()))
+        compare_array(case, name, got[name], ref[name], nx, ny, exact, loose, name in SWEEP_OUTPUTS.get(e, ()), special)
     if before is not None:
         for name, (dt, nx, ny, pk, role) in specs.items():
             if name not in OUTPUTS[e] and not (case.get("var") and name == "rd"):
                 assert np.array_equal(bits(got[name]), bits(before[name])), "mg_dev_%s case %s: input %s was modified" % (entry_name(case), case["id"], name)
     if ref_sum is not None or got_sum is not None:
         n_w, w_max = ref_ops.last_window
-        compare_sum(case, got_sum, ref_sum, n_w, w_max, NPDT[case["dt"]], exact)
+        compare_sum(case, got_sum, ref_sum, n_w, w_max, NPDT[case["dt"]], exact, special)

@@ -249,12 +249,21 @@ def test_scalars_kernel_and_breakdown():
     assert s[RZ] == 4.0 and s[ZQ] == 3.0 and s[BETA] == -(6.0 / 1500.0) * 3.0 / 3.0
     s = step(4, sc, [9.0, 16.0])
     assert s[RR] == 25.0 and s[8] == 25.0 and s[9] == 0.0
-    for bad in ([0.0], [-1.0, 0.5], [float("inf")], [float("nan")]):
+    for bad in ([0.0], [-1.0, 0.5], [float("inf")], [float("nan")], [float("-inf")], [0.5, float("nan"), 0.5], [0.5] * 2000 + [float("inf")]):
         step(0, sc, [1.0])
         s = step(3, sc, bad)
         assert s[FLAG] == 1.0 and s[ALPHA] == 0.0, bad
         s = step(4, sc, [1.0])
         assert s[9] == 1.0
+    # the other partial array: a non-finite r . z is a breakdown as well (alpha = rz / pq would be NaN or Inf with no flag)
+    for bad in ([float("nan")], [1.0, float("inf")], [float("-inf"), 1.0]):
+        s = step(0, sc, bad)
+        assert s[FLAG] == 0.0 and not math.isfinite(s[RZ]), bad
+        s = step(3, sc, [0.5])
+        assert s[FLAG] == 1.0 and s[ALPHA] == 0.0, bad
+    step(0, sc, [1.0])
+    s = step(3, sc, [0.5])
+    assert s[FLAG] == 0.0 and s[ALPHA] == 2.0
 
 
 # ------------------------------------------------------------------------------------------ 2. whole solves
