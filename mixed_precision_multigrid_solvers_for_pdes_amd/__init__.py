@@ -26,6 +26,7 @@ from .applications import MultigridPreconditioner, PoissonSolver2D
 from .krylov import PCGEngine, PCGSolver
 from .eigen import EigenEngine, EigenSolver
 from .flow import VorticityStreamSolver
+from .nonlinear import SemilinearEngine, SemilinearSolver
 
 __all__ = [
     "Grid", "BaseOperator", "LaplacianOperator", "DiffusionOperator", "HelmholtzOperator", "RestrictionOperator", "ProlongationOperator",
@@ -38,6 +39,6 @@ __all__ = [
     "MixedPrecisionMultigrid", "PoissonProblem", "default_max_levels",
     "PoissonSolver2D", "MultigridPreconditioner", "applications", "heat_equation", "HeatEquationSolver",
     "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver", "SeparableSource", "DeviceHeatStepper",
-    "EigenEngine", "EigenSolver", "VorticityStreamSolver",
+    "EigenEngine", "EigenSolver", "VorticityStreamSolver", "SemilinearEngine", "SemilinearSolver",
 ]
 __version__ = "0.1.0"

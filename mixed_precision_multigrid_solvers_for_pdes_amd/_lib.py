@@ -263,6 +263,45 @@ FLOW_SIGNATURES = {
     "mg_dev_flow_interior": (_i, [_i] * 3 + [_vp] * 6),
 }
 
+
+
+class MgNlOptions(C.Structure):
+    """mg_nl_options (include/mghip_nl.h)"""
+    _fields_ = [("forcing", C.c_int32), ("max_backtracks", C.c_int32), ("max_inner", C.c_int32), ("reserved", C.c_int32),
+                ("eta", C.c_double), ("gamma", C.c_double), ("eta_max", C.c_double), ("eta_min", C.c_double)]
+
+
+class MgNlStats(C.Structure):
+    """mg_nl_stats (include/mghip_nl.h)"""
+    _fields_ = [("solve_seconds", C.c_double), ("initial_residual", C.c_double), ("final_residual", C.c_double),
+                ("newton_iterations", C.c_int32), ("inner_iterations", C.c_int32), ("evaluations", C.c_int32),
+                ("status", C.c_int32)]
+
+
+MG_NL_LINEAR, MG_NL_CUBIC, MG_NL_SINH, MG_NL_EXP = 0, 1, 2, 3
+MG_NL_FORCING_EISENSTAT_WALKER, MG_NL_FORCING_FIXED = 0, 1
+NL_KINDS = {"linear": MG_NL_LINEAR, "cubic": MG_NL_CUBIC, "sinh": MG_NL_SINH, "exp": MG_NL_EXP}
+NL_FORCINGS = {"eisenstat_walker": MG_NL_FORCING_EISENSTAT_WALKER, "fixed": MG_NL_FORCING_FIXED}
+NL_STATUS = {0: "converged", 1: "max_newton", 2: "breakdown", 3: "line_search_failed"}
+
+# name -> (restype, argtypes); every symbol include/mghip_nl.h declares (the semilinear Newton method)
+NL_SIGNATURES = {
+    "mg_dev_nl_eval": (_i, [_i] * 4 + [_d] * 5 + [_vp] * 4 + [_d] + [_vp] * 7),
+    "mg_op_nl_eval": (_i, [_i] * 3 + [_d] * 5 + [_vp] * 4 + [_d] + [_vp] * 5),
+    "mg_pcg_set_reaction_device": (_i, [_vp, _vp, _i, _d]),
+    "mg_dev_pcg_direction_react": (_i, [_i] * 3 + [_d] * 4 + [_vp] * 10),
+    "mg_nl_create": (_i, [C.POINTER(MgConfig), _i, _i, C.POINTER(_vp)]),
+    "mg_nl_destroy": (_i, [_vp]),
+    "mg_nl_last_error": (C.c_char_p, [_vp]),
+    "mg_nl_options_default": (_i, [C.POINTER(MgNlOptions)]),
+    "mg_nl_set_coefficient": (_i, [_vp, _vp, _i]),
+    "mg_nl_set_shift": (_i, [_vp, _d]),
+    "mg_nl_set_nonlinearity": (_i, [_vp, _i, _d, _vp, _i]),
+    "mg_nl_set_options": (_i, [_vp, C.POINTER(MgNlOptions)]),
+    "mg_nl_solve": (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _pd, _pi, _pd, _pd, _i, _pi, _pi, C.POINTER(MgNlStats)]),
+    "mg_nl_solve_device": (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _pd, _pi, _pd, _pd, _i, _pi, _pi, C.POINTER(MgNlStats)]),
+}
+
 _lib = None
 
 
@@ -309,7 +348,7 @@ def load():
     _share_torch_hip_runtime()
     lib = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()) + \
-            list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()):
+            list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(NL_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib

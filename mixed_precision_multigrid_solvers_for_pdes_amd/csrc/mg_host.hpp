@@ -243,6 +243,15 @@ int d_ho_residual(const double* x, const double* g, double* r, double* partials,
                   double coeff, double sigma, hipStream_t st);
 void d_ho_rhs(const double* f, double* g, int nx, int ny, int ld, hipStream_t st);
 
+// mg_nl.hip: the one-pass kernel of the semilinear Newton method (mg_nl_kernels.hpp; include/mghip_nl.h), fp64 fields with
+// pitch ld.  v = u + t delta (delta NULL: u), F = (f - A v) - kappa w phi(v), c = kappa w phi'(v) (w NULL: 1); u_out, F and c
+// are nullable.  Returns the number of partials of the sum of F^2 at partials[0 ..]; as many of the sum of c start at
+// partials[*second] (second is even; 2 * max_partials(nx, ny) doubles hold both).  The Krylov loop (mg_pcg.hip) takes its
+// residuals under a reaction field from it: kind 0 (linear), kappa = 1, w = the field.
+int d_nl_eval(int kind, const double* u, const double* delta, double t, const double* a, const double* w, const double* f,
+              double* u_out, double* F, double* c, double* partials, int* second, int nx, int ny, int ld, double hx, double hy,
+              double coeff, double sigma, double kappa, hipStream_t st);
+
 // mg_engine.hip: what the solve loop (mg_solve.hip) and the stateless ABI (mg_dev.hip) use of the handle and cycle driver.
 // hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which a
 // hipStreamNonBlocking stream does not wait for: alloc_zero zeroes on the stream that will use the memory.

@@ -13,10 +13,15 @@
 // Under mg_pcg_set_order(4) (include/mghip_ho.h) A is the compact nine-point operator A4 and f is replaced by g = R f, formed
 // once per solve; the kernels are those of mg_ho.hip (d_ho_*), everything else -- the five-point preconditioner included -- is
 // the same code.
+//
+// Under mg_pcg_set_reaction_device (include/mghip_nl.h) A is A + diag(c) for a caller's field c: the direction kernel adds
+// c p to q, the initial and the true residual come from the Newton method's eval kernel in linear kind (mg_nl.hip,
+// d_nl_eval), and the engine preconditions with the scalar shift sigma + c_ref.  Without a field nothing here changes.
 #include "mg_launch.hpp"
 #include "mg_pcg_kernels.hpp"
 
 #include "../../include/mghip_ho.h"
+#include "../../include/mghip_nl.h"
 
 #include <atomic>
 
@@ -50,6 +55,8 @@ struct mg_pcg {
   bool varcoef = false;
   int order = 2;                        // 2: the five-point operator, 4: the compact nine-point scheme (mg_pcg_set_order)
   double* g = nullptr;                  // order 4: R f of the current solve (allocated when order 4 is first set)
+  const double* creact = nullptr;       // the caller's reaction field c (mg_pcg_set_reaction_device): A + diag(c); not owned
+  double c_ref = 0.0;                   // ... and the scalar the preconditioner stands in for it with: shift sigma + c_ref
   bool eng_has_rhs = false;
   hipEvent_t ev[2 * kTimedIters] = {};
   int nev = 0;
@@ -75,13 +82,15 @@ int stream_blocks(int nx, int nyv) {
 }
 
 // ---- launchers (shared by the driver and the stateless mg_dev_pcg_* forms); an int result is the number of partials ----
-int launch_direction(const double* z, const double* p_in, double* p_out, double* q, const double* a, const double* beta,
-                     double* partials, int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, hipStream_t st) {
+int launch_direction(const double* z, const double* p_in, double* p_out, double* q, const double* a, const double* creact,
+                     const double* beta, double* partials, int nx, int ny, int ld, double hx, double hy, double coeff, double sigma,
+                     hipStream_t st) {
   const mg::TileGeom g = pcg_geom(nx, ny, ld);
   const Coef c = coefs(hx, hy, sigma);
-  auto k = a ? mg::pcg_direction_kernel<true> : mg::pcg_direction_kernel<false>;
-  hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, z, p_in, p_out, q, a, beta, partials, g, c.ihx2, c.ihy2, c.diag,
-                     coeff, sigma);
+  auto k = creact ? (a ? mg::pcg_direction_kernel<true, true> : mg::pcg_direction_kernel<false, true>)
+                  : (a ? mg::pcg_direction_kernel<true, false> : mg::pcg_direction_kernel<false, false>);
+  hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, z, p_in, p_out, q, a, creact, beta, partials, g, c.ihx2, c.ihy2,
+                     c.diag, coeff, sigma);
   return g.ntiles;
 }
 
@@ -170,8 +179,8 @@ int front(mg_pcg* s, int k) {
   const double* beta = k == 0 ? nullptr : s->sc + mg::kPcgBeta;
   const int nq = s->order == 4
       ? d_ho_direction(s->z, p_old, s->p[nxt], s->q, beta, s->partials, s->nx, s->ny, s->ld, s->hx, s->hy, s->cfg.coeff, s->sigma, st)
-      : launch_direction(s->z, p_old, s->p[nxt], s->q, s->varcoef ? s->a : nullptr, beta, s->partials, s->nx, s->ny, s->ld, s->hx,
-                         s->hy, s->cfg.coeff, s->sigma, st);
+      : launch_direction(s->z, p_old, s->p[nxt], s->q, s->varcoef ? s->a : nullptr, s->creact, beta, s->partials, s->nx, s->ny,
+                         s->ld, s->hx, s->hy, s->cfg.coeff, s->sigma, st);
   s->cur = nxt;
   launch_scalars(mg::kPcgAlphaOp, s->partials, nq, nullptr, 0, s->sc, nullptr, 0, st);
   HIPC(&s->err, hipGetLastError());
@@ -233,11 +242,17 @@ int solve_resident(mg_pcg* s, double tol, int max_iter, double* hist, int hist_c
       const int n = d_sumsq(MG_F64, s->f, s->partials, ld, win[k][0], win[k][1], win[k][2], win[k][3], st);
       launch_reduce(s->partials, n, s->sc + kRing0 + k, st);
     }
-    if (s->varcoef) d_var(mg::kVarResidual, MG_F64, s->x, s->a, s->f, s->r, nx, ny, ld, s->hx, s->hy, 1.0, s->cfg.coeff, 0, 0, st, s->sigma);
-    else d_residual(MG_F64, s->x, s->f, s->r, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, false, s->sigma);
-    hipLaunchKernelGGL(mg::pcg_zero_ring_kernel, dim3(std::max(1, std::min(64, (2 * (nx + ny) + mg::kBlock - 1) / mg::kBlock))),
-                       dim3(mg::kBlock), 0, st, s->r, nx, ny, ld);
-    {
+    if (s->creact) {
+      // r = f - (A x + c x) with a zero ring and the sum of r^2 in one launch (the eval kernel, linear kind, w = c)
+      int second = 0;
+      const int n = d_nl_eval(MG_NL_LINEAR, s->x, nullptr, 0.0, s->varcoef ? s->a : nullptr, s->creact, s->f, nullptr, s->r, nullptr,
+                              s->partials, &second, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, s->sigma, 1.0, st);
+      launch_reduce(s->partials, n, s->sc + kRr0, st);
+    } else {
+      if (s->varcoef) d_var(mg::kVarResidual, MG_F64, s->x, s->a, s->f, s->r, nx, ny, ld, s->hx, s->hy, 1.0, s->cfg.coeff, 0, 0, st, s->sigma);
+      else d_residual(MG_F64, s->x, s->f, s->r, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, false, s->sigma);
+      hipLaunchKernelGGL(mg::pcg_zero_ring_kernel, dim3(std::max(1, std::min(64, (2 * (nx + ny) + mg::kBlock - 1) / mg::kBlock))),
+                         dim3(mg::kBlock), 0, st, s->r, nx, ny, ld);
       const int n = d_sumsq(MG_F64, s->r, s->partials, ld, 1, nx - 1, 1, ny - 1, st);
       launch_reduce(s->partials, n, s->sc + kRr0, st);
     }
@@ -272,7 +287,10 @@ int solve_resident(mg_pcg* s, double tol, int max_iter, double* hist, int hist_c
   }
   if (rc != MG_OK) { (void)hipStreamSynchronize(st); return rc; }
   // the true residual of the returned iterate, by the engine's own residual-norm kernels (what mg_residual_norm computes)
+  int second = 0;      // with a reaction field the eval kernel sums over interior cells only: the ring of f is added below
   const int nt = ho ? d_ho_residual(s->x, s->g, nullptr, s->partials, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, s->sigma, st)
+      : s->creact ? d_nl_eval(MG_NL_LINEAR, s->x, nullptr, 0.0, s->varcoef ? s->a : nullptr, s->creact, s->f, nullptr, nullptr, nullptr,
+                              s->partials, &second, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, s->sigma, 1.0, st)
       : s->varcoef
       ? d_var_residual_norm(MG_F64, s->x, s->a, s->f, s->partials, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, s->sigma)
       : d_residual_norm(MG_F64, s->x, s->f, s->partials, nx, ny, ld, s->hx, s->hy, s->cfg.coeff, st, false, s->sigma);
@@ -280,7 +298,7 @@ int solve_resident(mg_pcg* s, double tol, int max_iter, double* hist, int hist_c
   HIPC(&s->err, hipGetLastError());
   HIPC(&s->err, hipMemcpyAsync(s->h_sc, s->sc + kTrue, sizeof(double), hipMemcpyDeviceToHost, st));
   HIPC(&s->err, hipStreamSynchronize(st));           // also retires (and thereby drops) a queued lookahead
-  const double true_res = std::sqrt(hh * s->h_sc[0]);
+  const double true_res = std::sqrt(hh * (s->creact ? s->h_sc[0] + ring : s->h_sc[0]));
   const double t1 = now_s();
   double pre_ms = 0;
   const int timed = s->nev == 2 * kTimedIters ? std::min(fronts, kTimedIters) : 0;
@@ -402,6 +420,8 @@ int mg_pcg_set_order(mg_pcg* s, int order) {
   if (order != 2 && order != 4) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_order: order must be 2 or 4");
   if (order == 4 && s->varcoef)
     return pfail(s, MG_ERR_STATE, "mg_pcg_set_order: the fourth-order scheme needs constant coefficients (mg_pcg_set_coefficient(NULL) first)");
+  if (order == 4 && s->creact)
+    return pfail(s, MG_ERR_STATE, "mg_pcg_set_order: the fourth-order scheme takes no reaction field (mg_pcg_set_reaction_device(NULL) first)");
   if (order == 4 && !s->g) {
     HIPC(&s->err, hipSetDevice(s->cfg.device));
     const int rc = alloc_zero(&s->err, (void**)&s->g, field_bytes(s), s->eng->stream);
@@ -413,8 +433,27 @@ int mg_pcg_set_order(mg_pcg* s, int order) {
 
 int mg_pcg_set_shift(mg_pcg* s, double sigma) {
   if (!s || !(sigma >= 0.0) || !std::isfinite(sigma)) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_shift: sigma must be finite and >= 0");
-  ENG(mg_set_shift(s->eng, sigma));
+  ENG(mg_set_shift(s->eng, s->creact ? sigma + s->c_ref : sigma));
   s->sigma = sigma;
+  return MG_OK;
+}
+
+int mg_pcg_set_reaction_device(mg_pcg* s, const double* c_dev_or_null, int ld, double c_ref) {
+  if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: NULL solver");
+  if (!c_dev_or_null) {
+    if (s->creact) ENG(mg_set_shift(s->eng, s->sigma));
+    s->creact = nullptr;
+    s->c_ref = 0.0;
+    return MG_OK;
+  }
+  if (s->order == 4)
+    return pfail(s, MG_ERR_STATE, "mg_pcg_set_reaction_device: the fourth-order scheme takes no reaction field (mg_pcg_set_order(2) first)");
+  if (!(c_ref >= 0.0) || !std::isfinite(c_ref)) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: c_ref must be finite and >= 0");
+  if (ld != s->ld || !aligned16(c_dev_or_null))
+    return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: the field has the solver's pitch (mg_pitch_elems) and 16-byte alignment");
+  ENG(mg_set_shift(s->eng, s->sigma + c_ref));
+  s->creact = c_dev_or_null;
+  s->c_ref = c_ref;
   return MG_OK;
 }
 
@@ -455,8 +494,24 @@ int mg_dev_pcg_direction(int nx, int ny, int ld, double hx, double hy, double co
   CHECK_DEV(z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_pcg_direction: NULL pointer");
   CHECK_DEV(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null, "mg_dev_pcg_direction: p_out and q are arrays of their own");
   CHECK_DEV(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(a_or_null), "mg_dev_pcg_direction: unaligned pointer");
-  const int n = launch_direction(z, beta_dev_or_null ? p_in_or_null : nullptr, p_out, q, a_or_null, beta_dev_or_null, (double*)scratch,
-                                 nx, ny, ld, hx, hy, coeff, sigma, (hipStream_t)stream);
+  const int n = launch_direction(z, beta_dev_or_null ? p_in_or_null : nullptr, p_out, q, a_or_null, nullptr, beta_dev_or_null,
+                                 (double*)scratch, nx, ny, ld, hx, hy, coeff, sigma, (hipStream_t)stream);
+  launch_reduce((double*)scratch, n, pq_dev, (hipStream_t)stream);
+  HIPC(nullptr, hipGetLastError());
+  return MG_OK;
+}
+
+int mg_dev_pcg_direction_react(int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, const double* a_or_null,
+                               const double* c, const double* z, const double* p_in_or_null, double* p_out, double* q,
+                               const double* beta_dev_or_null, void* scratch, double* pq_dev, void* stream) {
+  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && sigma >= 0.0, "mg_dev_pcg_direction_react: bad shape / pitch / shift");
+  CHECK_DEV(c && z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_pcg_direction_react: NULL pointer");
+  CHECK_DEV(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null && p_out != c && q != c,
+            "mg_dev_pcg_direction_react: p_out and q are arrays of their own");
+  CHECK_DEV(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(a_or_null) && aligned16(c),
+            "mg_dev_pcg_direction_react: unaligned pointer");
+  const int n = launch_direction(z, beta_dev_or_null ? p_in_or_null : nullptr, p_out, q, a_or_null, c, beta_dev_or_null,
+                                 (double*)scratch, nx, ny, ld, hx, hy, coeff, sigma, (hipStream_t)stream);
   launch_reduce((double*)scratch, n, pq_dev, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;

@@ -6,7 +6,7 @@
 // (block_reduce_sum) followed by a fixed-order pass of one workgroup: no atomics, the same bits on every run.  Pad columns
 // (>= ny) are masked out of the sums and never stored.
 //
-// Per iteration and cell: direction 4 words (z, p in, p out, q; 5 with the coefficient), update 6 (p, q, x in/out, r in/out),
+// Per iteration and cell: direction 4 words (z, p in, p out, q; one more with the coefficient, one more with a reaction field), update 6 (p, q, x in/out, r in/out),
 // dots 2 (r, z; 3 with q for the flexible beta).
 #pragma once
 
@@ -21,11 +21,14 @@ namespace mg {
 //   of its OWN: a neighbouring workgroup reads the old p on this tile's edge cells as its halo, so an in-place update would
 //   race across workgroups.  The operator expression is residual_kernel's / varcoef_kernel's own: q == -(f - A p') with f = 0.
 //   Stored: exactly the cells [0, nx) x [0, ny) of p_out and q (0 on the ring).
+//   REACT (include/mghip_nl.h, mg_pcg_set_reaction_device): the operator is A + diag(c), q = q0 + c*p' with q0 the expression
+//   above; c is read once per cell straight into registers (its ring and pad are loaded and not used).
 // --------------------------------------------------------------------------------------------
-template <bool VAR>
+template <bool VAR, bool REACT>
 __global__ __launch_bounds__(kBlock) void pcg_direction_kernel(const double* __restrict__ z, const double* __restrict__ p_in,
                                                                double* __restrict__ p_out, double* __restrict__ q,
-                                                               const double* __restrict__ a, const double* __restrict__ beta_ptr,
+                                                               const double* __restrict__ a, const double* __restrict__ creact,
+                                                               const double* __restrict__ beta_ptr,
                                                                double* __restrict__ partials, TileGeom g, double ihx2, double ihy2,
                                                                double diag, double coeff, double sigma) {
   using S = TileShape<double>;
@@ -36,6 +39,16 @@ __global__ __launch_bounds__(kBlock) void pcg_direction_kernel(const double* __r
   const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
   const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
   const double beta = beta_ptr ? *beta_ptr : 0.0;
+
+  Pack<double> cr[REACT ? S::RPT : 1];
+  if (REACT) {
+    const int cgr = threadIdx.x % S::CG, rgr = threadIdx.x / S::CG;
+#pragma unroll
+    for (int k = 0; k < S::RPT; ++k) {
+      const int gi = i0 + rgr * S::RPT + k, gj = j0 + cgr * S::N;
+      cr[REACT ? k : 0] = (gi < g.nx && gj < g.nyv) ? ldg(creact + (size_t)gi * g.ld + gj) : zero_pack<double>();
+    }
+  }
 
   for (int v = threadIdx.x; v < (kTI + 2) * S::VPR; v += kBlock) {
     const int r = v / S::VPR, c = v - r * S::VPR;
@@ -99,6 +112,7 @@ __global__ __launch_bounds__(kBlock) void pcg_direction_kernel(const double* __r
       } else {
         au = coeff * (((dn.v[e] + up.v[e]) * ihx2 + (ea + w) * ihy2) - mid.v[e] * diag);
       }
+      if (REACT) au = au + cr[REACT ? k : 0].v[e] * mid.v[e];
       const int gj = gj0 + e;
       const bool interior = row_in && gj >= 1 && gj < g.ny - 1;
       o.v[e] = interior ? au : 0.0;
