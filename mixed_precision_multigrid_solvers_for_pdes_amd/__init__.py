@@ -27,6 +27,7 @@ from .krylov import PCGEngine, PCGSolver
 from .eigen import EigenEngine, EigenSolver
 from .flow import VorticityStreamSolver
 from .nonlinear import SemilinearEngine, SemilinearSolver
+from .reaction_diffusion import ReactionDiffusionSolver
 
 __all__ = [
     "Grid", "BaseOperator", "LaplacianOperator", "DiffusionOperator", "HelmholtzOperator", "RestrictionOperator", "ProlongationOperator",
@@ -40,5 +41,6 @@ __all__ = [
     "PoissonSolver2D", "MultigridPreconditioner", "applications", "heat_equation", "HeatEquationSolver",
     "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver", "SeparableSource", "DeviceHeatStepper",
     "EigenEngine", "EigenSolver", "VorticityStreamSolver", "SemilinearEngine", "SemilinearSolver",
+    "ReactionDiffusionSolver",
 ]
 __version__ = "0.1.0"

@@ -302,6 +302,38 @@ NL_SIGNATURES = {
     "mg_nl_solve_device": (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _pd, _pi, _pd, _pd, _i, _pi, _pi, C.POINTER(MgNlStats)]),
 }
 
+
+
+class MgRdStepInfo(C.Structure):
+    """mg_rd_step_info (include/mghip_rd.h)"""
+    _fields_ = [("lambda", C.c_double), ("rhs_norm", C.c_double), ("initial_residual", C.c_double),
+                ("final_residual", C.c_double), ("solve_seconds", C.c_double), ("newton_iterations", C.c_int32),
+                ("inner_iterations", C.c_int32), ("evaluations", C.c_int32), ("status", C.c_int32), ("converged", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+RD_SCHEMES = {"implicit_euler": MG_HEAT_IMPLICIT_EULER, "crank_nicolson": MG_HEAT_CRANK_NICOLSON, "bdf2": MG_HEAT_BDF2}
+
+# name -> (restype, argtypes); every symbol include/mghip_rd.h declares (the reaction-diffusion stepper)
+RD_SIGNATURES = {
+    "mg_dev_rd_rhs": (_i, [_i] * 5 + [_d] * 6 + [_vp] * 5 + [_d] * 2 + [_vp] * 4),
+    "mg_dev_rd_energy": (_i, [_i] * 4 + [_d] * 2 + [_vp] * 6),
+    "mg_rd_create": (_i, [C.POINTER(MgConfig), _d, _i, _i, C.POINTER(_vp)]),
+    "mg_rd_destroy": (_i, [_vp]),
+    "mg_rd_last_error": (C.c_char_p, [_vp]),
+    "mg_rd_set_slot": (_i, [_vp, _i, _vp, _i]),
+    "mg_rd_get_slot": (_i, [_vp, _i, _vp, _i]),
+    "mg_rd_set_slot_device": (_i, [_vp, _i, _vp, _i, _i]),
+    "mg_rd_get_slot_device": (_i, [_vp, _i, _vp, _i, _i]),
+    "mg_rd_set_coefficient": (_i, [_vp, _vp, _i]),
+    "mg_rd_set_source": (_i, [_vp, _vp, _i]),
+    "mg_rd_set_reaction": (_i, [_vp, _i, _d, _vp, _i, _d]),
+    "mg_rd_set_newton_options": (_i, [_vp, C.POINTER(MgNlOptions)]),
+    "mg_rd_step": (_i, [_vp, _i, _d, _i, _i, _i, _d, _d, _pd, _d, _i, C.POINTER(MgRdStepInfo)]),
+    "mg_rd_energy": (_i, [_vp, _i, _pd]),
+    "mg_rd_diff_norm": (_i, [_vp, _i, _i, _pd]),
+}
+
 _lib = None
 
 
@@ -348,7 +380,8 @@ def load():
     _share_torch_hip_runtime()
     lib = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()) + \
-            list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(NL_SIGNATURES.items()):
+            list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(NL_SIGNATURES.items()) + \
+            list(RD_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -19,6 +19,7 @@
 #include "mg_kernels.hpp"
 
 struct mg_line_plan;   // mg_line.hip: the tables of one (dtype, direction, shape, spacings, sigma) of the zebra line smoothers
+struct mg_nl;          // mg_nl.hip: the semilinear Newton driver
 
 namespace mgh {
 
@@ -268,6 +269,9 @@ void rhs_ring_is_zero(mg_handle* h);
 // mg_pcg.hip: the preconditioner engine an mg_pcg owns (its stream carries all of the solver's work), for the unit of the
 // library that owns an mg_pcg (mg_heat.hip) and queues its own kernels in between
 mg_handle* pcg_engine(mg_pcg* s);
+// mg_nl.hip: the same engine through the mg_nl that owns the mg_pcg, for the unit of the library that owns an mg_nl
+// (mg_rd.hip): its stream carries the Newton method's work and the stepper's kernels in between
+mg_handle* nl_engine(mg_nl* s);
 void inject_rings(mg_handle* h, int ph, bool only_shared = false);
 void inject_rings_once(mg_handle* h, int p);
 // `part` (level 0 only) splits the fused cycle for speculative launching: the FRONT part (down leg + the whole

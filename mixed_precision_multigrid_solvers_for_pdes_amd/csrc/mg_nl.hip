@@ -70,6 +70,10 @@ struct mg_nl {
   std::string err;
 };
 
+namespace mgh {
+mg_handle* nl_engine(mg_nl* s) { return pcg_engine(s->pcg); }
+}  // namespace mgh
+
 namespace {
 
 bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
