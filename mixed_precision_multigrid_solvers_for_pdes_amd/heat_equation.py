@@ -112,11 +112,12 @@ class SeparableSource:
 class HeatEquationSolver:
     """du/dt = alpha Laplace(u) + f  (heat_equation.py:75-600), implicit steps by shifted multigrid on the GPU.
     device_resident=True also takes conductivity= (a callable a(x, y) or an (nx, ny) array: du/dt = alpha div(a grad u) + f),
-    inner_solver="multigrid" | "pcg" and, for PCG, inner_precision="double" | "single_managed" | "mixed"."""
+    inner_solver="multigrid" | "pcg" and, for PCG, inner_precision="double" | "single_managed" | "mixed".  coarse_direct: as
+    MultigridEngine's (None: the default, a direct coarsest solve)."""
 
     def __init__(self, config: HeatEquationConfig, grid: Grid, precision_manager: Optional[PrecisionManager] = None,
                  device_id: int = 0, max_levels: int = 32, smoother: str = "jacobi", device_resident: bool = False,
-                 conductivity=None, inner_solver: str = "multigrid", inner_precision: str = "double"):
+                 conductivity=None, inner_solver: str = "multigrid", inner_precision: str = "double", coarse_direct=None):
         self.config = config
         self.grid = grid
         self.precision_manager = precision_manager or PrecisionManager()
@@ -152,13 +153,14 @@ class HeatEquationSolver:
             self.stepper = DeviceHeatStepper(grid.nx, grid.ny, tuple(float(v) for v in grid.domain),
                                              config.thermal_diffusivity, max_levels, sm, omega, device=device_id,
                                              inner="pcg" if inner_solver == "pcg" else "cycle",
-                                             precision=inner_precision if inner_solver == "pcg" else "double")
+                                             precision=inner_precision if inner_solver == "pcg" else "double",
+                                             coarse_direct=coarse_direct)
             self.mg_solver = None
             self._cur = 0                # slot of the current solution
             self._bdf_prev = None        # (slot of the level before it, the dt that led from there to _cur)
         else:
             self.mg_solver = MultigridEngine(grid.nx, grid.ny, tuple(float(v) for v in grid.domain), -1.0, max_levels, "V",
-                                             2, 2, sm, omega, device=device_id)
+                                             2, 2, sm, omega, device=device_id, coarse_direct=coarse_direct)
         self.laplacian = LaplacianOperator(coefficient=1.0)
         self.current_time = 0.0
         self.current_solution = None

@@ -44,11 +44,12 @@ class ReactionDiffusionSolver:
     """One mg_rd on a Grid.  tolerance: every step's Newton solve stops at ||F||_h < tolerance * max(1, ||f||_h); precision is
     the PRECONDITIONER's ("double", "single_managed", "mixed"; the state is fp64).  source: a SeparableSource(profile, factor),
     or an (nx, ny) array (a steady source, g == 1).  conductivity: an (nx, ny) array or a callable a(x, y) > 0.  weight >= 0.
-    step() returns the info dict of mg_rd_step_info; energy() the discrete free energy and its three sums."""
+    step() returns the info dict of mg_rd_step_info; energy() the discrete free energy and its three sums.  coarse_direct: as
+    MultigridEngine's (None: the default, the coarsest grid of the preconditioner's cycle is solved directly)."""
 
     def __init__(self, grid, diffusivity, nonlinearity="cubic", strength=1.0, weight=None, linear_growth=0.0, conductivity=None,
                  source=None, scheme="bdf2", max_levels=None, tolerance=1e-8, precision="double", smoother=None, max_newton=30,
-                 forcing="eisenstat_walker"):
+                 forcing="eisenstat_walker", coarse_direct=None):
         from .engine import _direct_code
         from .facade import default_max_levels
         # every refusal below happens before the library loads
@@ -115,7 +116,7 @@ class ReactionDiffusionSolver:
         lib = _lib.load()
         cfg = _lib.MgConfig(self.nx, self.ny, float(d[0]), float(d[1]), float(d[2]), float(d[3]), -1.0, levels, _lib.MG_CYCLE_V, 2, 2,
                             int(smoother.kind), float(smoother.omega), 1e-12, 1000, PRECISIONS[precision], 1e-6, 4.0, 0, 0, 0, 0, 2,
-                            1, 0, 2, _direct_code(None), 0)
+                            1, 0, 2, _direct_code(coarse_direct), 0)
         self.cfg = cfg
         self._lib = lib
         self._h = C.c_void_p(None)

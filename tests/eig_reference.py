@@ -157,11 +157,12 @@ PINNED_ITERATIONS = {"A": 18, "A32": 18, "B": 16, "C": 16, "D": 15}
 TOL = 1e-8
 
 
-def case_oracle(name):
+def case_oracle(name, oracle_classes=None):
+    """oracle_classes: as pcg_reference.make_oracle's (None: the pinned pair)"""
     c = CASES[name]
     a = jump_coefficient(c["nx"], c["ny"]) if c["a"] == "jump" else None
     return R.make_oracle(c["nx"], c["ny"], a=a, pre=c["pre"], post=c["post"], smoother=c["smoother"],
-                         omega=0.8 if c["smoother"] == "jacobi" else 1.0, domain=c["domain"])
+                         omega=0.8 if c["smoother"] == "jacobi" else 1.0, domain=c["domain"], oracle_classes=oracle_classes)
 
 
 def case_exact(name):
@@ -185,11 +186,11 @@ def case_exact(name):
 _RUNS = {}
 
 
-def run_case(name, tol=TOL, max_iterations=100):
+def run_case(name, tol=TOL, max_iterations=100, oracle_classes=None):
     """the restatement on a case from the default start, computed once per process"""
-    key = (name, tol, max_iterations)
+    key = (name, tol, max_iterations, oracle_classes)
     if key not in _RUNS:
         c = CASES[name]
-        _RUNS[key] = lobpcg(case_oracle(name), default_start(c["m"], c["nx"], c["ny"]), c["k"], tol=tol,
+        _RUNS[key] = lobpcg(case_oracle(name, oracle_classes), default_start(c["m"], c["nx"], c["ny"]), c["k"], tol=tol,
                             max_iterations=max_iterations, pm=R.precision_manager(c["precision"]))
     return _RUNS[key]

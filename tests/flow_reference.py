@@ -142,7 +142,8 @@ class SineSolver:
 class CycleSolver:
     """the pinned oracle's cycle from `guess` to ||r|| < tol max(1, ||f||_h) (tol = 0: exactly max_cycles cycles)"""
 
-    def __init__(self, nx, ny, domain=UNIT, tol=1e-10, max_cycles=50, smoother="jacobi", omega=0.8, max_levels=32):
+    def __init__(self, nx, ny, domain=UNIT, tol=1e-10, max_cycles=50, smoother="jacobi", omega=0.8, max_levels=32, oracle_cls=None):
+        self.oracle_cls = oracle_cls                   # None: the pinned MGOracle; or tests/coarse_exact_reference.ExactCoarseOracle
         self.nx, self.ny, self.domain = nx, ny, domain
         self.hx, self.hy = O.grid_spacing(nx, ny, domain)
         self.tol, self.max_cycles = tol, max_cycles
@@ -150,7 +151,7 @@ class CycleSolver:
 
     def __call__(self, f, guess, shift):
         fnorm = float(np.sqrt(self.hx * self.hy * np.sum(f * f)))
-        mgo = O.MGOracle(self.nx, self.ny, shift=shift, **self.kw)
+        mgo = (self.oracle_cls or O.MGOracle)(self.nx, self.ny, shift=shift, **self.kw)
         out, info = mgo.solve(f, guess, tol=self.tol * max(1.0, fnorm), max_iterations=self.max_cycles)
         return out, {"cycles": info["iterations"], "final_residual": info["final_residual"], "converged": info["converged"],
                      "rhs_norm": fnorm}

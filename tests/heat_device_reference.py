@@ -55,8 +55,9 @@ def set_ring(u, edge4):
 
 
 def step(scheme, u, dt, a, domain=(0.0, 1.0, 0.0, 1.0), u_prev=None, S=None, g0=1.0, g1=1.0, edge4=None, bc_before_solve=False,
-         tol=1e-10, max_cycles=20, smoother="jacobi", omega=0.8, max_levels=32):
-    """one step: (u_new, info) with info = lambda, rhs_norm, final_residual, cycles"""
+         tol=1e-10, max_cycles=20, smoother="jacobi", omega=0.8, max_levels=32, oracle_cls=None):
+    """one step: (u_new, info) with info = lambda, rhs_norm, final_residual, cycles; oracle_cls: the hierarchy's class (None: the pinned
+    MGOracle, looked up at the call; or tests/coarse_exact_reference.ExactCoarseOracle)"""
     nx, ny = u.shape
     hx, hy = O.grid_spacing(nx, ny, domain)
     if scheme == EXPLICIT:
@@ -70,7 +71,7 @@ def step(scheme, u, dt, a, domain=(0.0, 1.0, 0.0, 1.0), u_prev=None, S=None, g0=
     if bc_before_solve:
         set_ring(guess, edge4)
     fnorm = float(np.sqrt(hx * hy * np.sum(f * f)))
-    mgo = O.MGOracle(nx, ny, domain=domain, max_levels=max_levels, cycle="V", pre=2, post=2, smoother=smoother, omega=omega, shift=lm)
+    mgo = (oracle_cls or O.MGOracle)(nx, ny, domain=domain, max_levels=max_levels, cycle="V", pre=2, post=2, smoother=smoother, omega=omega, shift=lm)
     out, info = mgo.solve(f, guess, tol=tol * max(1.0, fnorm), max_iterations=max_cycles)
     if not bc_before_solve and edge4 is not None:
         set_ring(out, edge4)

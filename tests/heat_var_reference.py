@@ -47,15 +47,16 @@ def rhs_var(scheme, u, dt, alpha, a, hx, hy, u_prev=None, S=None, g0=1.0, g1=1.0
     return out
 
 
-def inner_oracle(a, lm, domain=(0.0, 1.0, 0.0, 1.0), smoother="jacobi", omega=0.8, max_levels=32):
-    """the stepper's inner hierarchy: V(2, 2) of -div(a grad) + lambda"""
-    return O.VarMGOracle(np.asarray(a, dtype=np.float64), domain=domain, max_levels=max_levels, cycle="V", pre=2, post=2,
+def inner_oracle(a, lm, domain=(0.0, 1.0, 0.0, 1.0), smoother="jacobi", omega=0.8, max_levels=32, oracle_cls=None):
+    """the stepper's inner hierarchy: V(2, 2) of -div(a grad) + lambda; oracle_cls: its class (None: the pinned VarMGOracle; or
+    tests/coarse_exact_reference.ExactCoarseVarOracle)"""
+    return (oracle_cls or O.VarMGOracle)(np.asarray(a, dtype=np.float64), domain=domain, max_levels=max_levels, cycle="V", pre=2, post=2,
                          smoother=smoother, omega=omega, shift=lm)
 
 
 def step_var(scheme, u, dt, alpha, a, domain=(0.0, 1.0, 0.0, 1.0), u_prev=None, S=None, g0=1.0, g1=1.0, edge4=None,
              bc_before_solve=False, tol=1e-10, max_cycles=20, smoother="jacobi", omega=0.8, max_levels=32, inner="cycle", pm=None,
-             flexible=None):
+             flexible=None, oracle_cls=None):
     """one step: (u_new, info) with info = lambda, rhs_norm, final_residual, cycles, converged"""
     nx, ny = u.shape
     hx, hy = O.grid_spacing(nx, ny, domain)
@@ -70,7 +71,7 @@ def step_var(scheme, u, dt, alpha, a, domain=(0.0, 1.0, 0.0, 1.0), u_prev=None, 
     if bc_before_solve:
         R.set_ring(guess, edge4)
     fnorm = float(np.sqrt(hx * hy * np.sum(f * f)))
-    mgo = inner_oracle(a, lm, domain, smoother, omega, max_levels)
+    mgo = inner_oracle(a, lm, domain, smoother, omega, max_levels, oracle_cls)
     if inner == "cycle":
         out, info = mgo.solve(f, guess, tol=tol * max(1.0, fnorm), max_iterations=max_cycles)
         final, cycles, conv = info["final_residual"], info["iterations"], info["converged"]

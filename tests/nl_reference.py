@@ -79,7 +79,8 @@ def norm_h(F, hx, hy):
 class Problem:
     """A u + kappa w phi(u) = f on an (nx, ny) grid of `domain`"""
 
-    def __init__(self, kind, nx, ny, kappa, a=None, w=None, coeff=-1.0, sigma=0.0, domain=(0.0, 1.0, 0.0, 1.0)):
+    def __init__(self, kind, nx, ny, kappa, a=None, w=None, coeff=-1.0, sigma=0.0, domain=(0.0, 1.0, 0.0, 1.0), oracle_classes=None):
+        self.oracle_classes = oracle_classes           # what .oracle() builds from (pcg_reference.make_oracle); None: the pinned pair
         self.kind = KINDS[kind] if isinstance(kind, str) else kind
         self.nx, self.ny, self.kappa, self.a, self.w, self.coeff, self.sigma, self.domain = nx, ny, kappa, a, w, coeff, sigma, domain
         self.hx, self.hy = (domain[1] - domain[0]) / (nx - 1), (domain[3] - domain[2]) / (ny - 1)
@@ -95,7 +96,8 @@ class Problem:
         return norm_h(F, self.hx, self.hy)
 
     def oracle(self, shift, pre=2, post=2, smoother="jacobi", omega=0.8):
-        return R.make_oracle(self.nx, self.ny, self.a, pre, post, smoother, omega, shift=self.sigma + shift, domain=self.domain)
+        return R.make_oracle(self.nx, self.ny, self.a, pre, post, smoother, omega, shift=self.sigma + shift, domain=self.domain,
+                             oracle_classes=self.oracle_classes)
 
 
 def mesh(nx, ny, domain=(0.0, 1.0, 0.0, 1.0)):

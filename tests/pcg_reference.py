@@ -41,10 +41,13 @@ def random_rhs(nx, ny, seed=0):
 
 
 def make_oracle(nx, ny, a=None, pre=1, post=1, smoother="jacobi", omega=0.8, cycle="V", max_levels=None, shift=0.0,
-                domain=(0.0, 1.0, 0.0, 1.0)):
+                domain=(0.0, 1.0, 0.0, 1.0), oracle_classes=None):
+    """oracle_classes: (constant-coefficient class, variable-coefficient class) to build the hierarchy from -- None: the pinned
+    MGOracle / VarMGOracle; tests/coarse_exact_reference.py has the pair with an exact coarsest solve"""
+    const_cls, var_cls = oracle_classes or (O.MGOracle, O.VarMGOracle)
     kw = dict(domain=domain, max_levels=max_levels or full_levels(nx, ny), cycle=cycle, pre=pre, post=post, smoother=smoother,
               omega=omega, jacobi_form="vectorized", shift=shift)
-    return O.MGOracle(nx, ny, **kw) if a is None else O.VarMGOracle(np.asarray(a, dtype=np.float64), **kw)
+    return const_cls(nx, ny, **kw) if a is None else var_cls(np.asarray(a, dtype=np.float64), **kw)
 
 
 def precision_manager(precision):

@@ -85,18 +85,22 @@ def energy(kind, u, hx, hy, alpha, kappa, rho, a=None, w=None):
 
 
 def step(scheme, kind, u, dt, alpha, kappa=0.0, rho=0.0, domain=(0.0, 1.0, 0.0, 1.0), u_prev=None, S=None, a=None, w=None, g0=1.0,
-         g1=1.0, edge4=None, tol=1e-10, max_newton=50):
-    """one step with the dense exact Newton method: (u_new, info); the tolerance is tol * max(1, ||f||_h), as the driver's"""
+         g1=1.0, edge4=None, tol=1e-10, max_newton=50, inner="dense", oracle_classes=None, **newton_kw):
+    """one step with the dense exact Newton method: (u_new, info); the tolerance is tol * max(1, ||f||_h), as the driver's.
+    inner="pcg": the driver's own Newton - conjugate gradients - multigrid loop restated (nl_reference.newton) on the hierarchy
+    classes `oracle_classes` (None: the pinned pair), with nl_reference.newton's keywords in newton_kw"""
     nx, ny = u.shape
-    p = NL.Problem(kind, nx, ny, kappa / alpha, a=a, w=w, coeff=-1.0, sigma=lam(scheme, dt, alpha), domain=domain)
+    p = NL.Problem(kind, nx, ny, kappa / alpha, a=a, w=w, coeff=-1.0, sigma=lam(scheme, dt, alpha), domain=domain,
+                   oracle_classes=oracle_classes)
     f = rhs(scheme, p.kind, u, dt, alpha, p.hx, p.hy, kappa, rho, u_prev, S, a, w, g0, g1)
     guess = u.copy()
     if edge4 is not None:
         set_ring(guess, edge4)
     fnorm = float(np.sqrt(p.hx * p.hy * np.sum(f * f)))
-    out, info = NL.newton(p, f, guess, tol * max(1.0, fnorm), max_newton=max_newton, inner="dense")
+    out, info = NL.newton(p, f, guess, tol * max(1.0, fnorm), max_newton=max_newton, inner=inner, **newton_kw)
     return out, {"lambda": p.sigma, "rhs_norm": fnorm, "initial_residual": info["initial_residual"],
                  "final_residual": info["true_residual"], "newton_iterations": info["newton_iterations"],
+                 "inner_iterations": info["inner_iterations"],
                  "converged": info["converged"]}
 
 
