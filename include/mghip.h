@@ -187,7 +187,11 @@ int mg_set_rhs(mg_handle* h, const void* rhs, int host_dtype);
 int mg_set_solution(mg_handle* h, const void* u0_or_null, int host_dtype);
 int mg_get_solution(mg_handle* h, void* u_out, int host_dtype);
 int mg_cycle(mg_handle* h, int ncycles);           /* asynchronous on the handle's stream        */
-/* full-multigrid initial guess from the resident rhs (replaces solvers/advanced_multigrid.py:626-683), asynchronous */
+/* full-multigrid initial guess from the resident rhs and the boundary ring of the resident iterate, whose interior is ignored
+   (replaces solvers/advanced_multigrid.py:626-683), asynchronous.  MG_PREC_DEFECT: the walk runs on the error equation
+   A e = f - A u of the WHOLE resident iterate u, interior included, from the zero correction, and the iterate becomes u + e:
+   after mg_set_solution(NULL) or a ring-only u that is a full-multigrid guess for these boundary data, after a u with a
+   non-zero interior it is one full-multigrid correction of that u (the interior is NOT ignored). */
 int mg_fmg(mg_handle* h, int cycles_per_level);
 int mg_residual_norm(mg_handle* h, double* out);   /* sqrt(hx*hy*sum r^2), synchronises           */
 int mg_set_working_precision(mg_handle* h, int dtype); /* MG_PREC_ADAPTIVE only: in-device cast of u */

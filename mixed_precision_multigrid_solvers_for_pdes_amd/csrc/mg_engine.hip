@@ -479,8 +479,11 @@ void inject_rings_once(mg_handle* h, int p) {
 }
 
 // Full-multigrid start under defect correction (MG_PREC_DEFECT): the fp32 hierarchy solves the ERROR equation, so the FMG
-// pass runs on A e = f - A u0 (u0: the Dirichlet ring of the fp64 iterate, zero inside) from the zero correction, and the
-// result is added to the fp64 iterate -- the defect loop then starts from u0 + e instead of discarding the FMG work.
+// pass runs on A e = f - A u0 from the zero correction, u0 the WHOLE resident fp64 iterate, interior included (mg_solve calls it
+// with the Dirichlet ring alone: FMG only without an initial guess; after mg_set_solution(u0) + mg_fmg the interior of u0 is
+// part of the defect), and the result is added to the fp64 iterate -- the defect loop then starts from u0 + e instead of
+// discarding the FMG work.  Unlike fmg_init under the other policies it does not forget the interior of the iterate: the
+// answer is u0 + e, never a guess built from f and the ring alone (tests/test_gpu_defect_policy.py pins both starts).
 int defect_fmg(mg_handle* h, int ncyc) {
   if (h->varcoef) return MG_ERR_INVALID_VALUE;
   if (h->L() < 2) return MG_OK;

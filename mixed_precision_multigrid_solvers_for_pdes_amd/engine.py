@@ -164,7 +164,8 @@ class MultigridEngine:
         self._check(self._lib.mg_cycle(self._h, int(n)))
 
     def fmg(self, cycles_per_level=1):
-        """Full-multigrid initial guess from the resident rhs (the boundary ring of the current iterate is kept)."""
+        """Full-multigrid initial guess from the resident rhs (the boundary ring of the current iterate is kept).  Under
+        MG_PREC_DEFECT the walk corrects the whole resident iterate, interior included: u <- u + e (include/mghip.h mg_fmg)."""
         self._check(self._lib.mg_fmg(self._h, int(cycles_per_level)))
 
     def residual_norm(self):

@@ -397,7 +397,8 @@ def test_flow_stepper_is_usable_after_poison():
 # ======================================================================================================================
 # 4. mg_handle after a poisoned solve
 # ======================================================================================================================
-PRECISIONS = {"double": _lib.MG_PREC_DOUBLE, "single": _lib.MG_PREC_SINGLE, "mixed": _lib.MG_PREC_MIXED_LEVELS, "adaptive": _lib.MG_PREC_ADAPTIVE}
+PRECISIONS = {"double": _lib.MG_PREC_DOUBLE, "single": _lib.MG_PREC_SINGLE, "mixed": _lib.MG_PREC_MIXED_LEVELS, "adaptive": _lib.MG_PREC_ADAPTIVE,
+              "defect": _lib.MG_PREC_DEFECT}
 
 
 def _handle(n, precision, speculate):
