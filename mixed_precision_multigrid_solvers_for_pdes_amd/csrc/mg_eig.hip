@@ -47,20 +47,7 @@ struct mg_eig {
 
 namespace {
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-bool ld_ok(int ny, int ld) { return ld >= ny && ld % 2 == 0; }
 int nyv_of(int ny, int ld) { return std::min(ld, (ny + 1) / 2 * 2); }
-
-mg::TileGeom tile_geom(int nx, int ny, int ld) {
-  using S = mg::TileShape<double>;
-  mg::TileGeom g;
-  g.nx = nx; g.ny = ny; g.ld = ld;
-  g.nyv = nyv_of(ny, ld);
-  g.i_org = 0;
-  g.tiles_j = (ny + S::TJ - 1) / S::TJ;
-  g.ntiles = (nx + mg::kTI - 1) / mg::kTI * g.tiles_j;
-  return g;
-}
 
 int stream_blocks(long long vecs, int cap) {
   return (int)std::max<long long>(1, std::min<long long>((vecs + mg::kBlock - 1) / mg::kBlock, cap));
@@ -69,7 +56,7 @@ int stream_blocks(long long vecs, int cap) {
 // ---- launchers (shared by the driver and the stateless mg_dev_eig_* forms) ----
 void launch_apply(const double* v, double* av, const double* a, int ncols, long long cs, int nx, int ny, int ld, double hx, double hy,
                   double coeff, hipStream_t st) {
-  const mg::TileGeom g = tile_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const Coef c = coefs(hx, hy, 0.0);
   auto k = a ? mg::eig_apply_kernel<true> : mg::eig_apply_kernel<false>;
   hipLaunchKernelGGL(k, dim3(g.ntiles, 1, ncols), dim3(mg::kBlock), 0, st, v, av, a, cs, g, c.ihx2, c.ihy2, c.diag, coeff);
@@ -137,13 +124,6 @@ void launch_residual(int ncols, const double* x, const double* ax, const double*
   hipLaunchKernelGGL(mg::eig_reduce_cols_kernel, dim3(ncols), dim3(mg::kBlock), 0, st, scratch, nb, sumsq_dev);
 }
 
-int efail(mg_eig* s, int code, const std::string& msg) { return fail(s ? &s->err : nullptr, code, msg); }
-int eng_rc(mg_eig* s, int rc) {
-  if (rc != MG_OK) efail(s, rc, std::string("preconditioner: ") + mg_last_error(s->eng));
-  return rc;
-}
-#define ENG(call) do { const int rc_ = eng_rc(s, (call)); if (rc_ != MG_OK) return rc_; } while (0)
-
 void release(mg_eig* s) {
   if (s->eng) { (void)mg_destroy(s->eng); s->eng = nullptr; }
   for (double** p : {&s->blk[0], &s->blk[1], &s->a, &s->staging, &s->scratch, &s->g_dev, &s->coef_dev, &s->lam_dev, &s->sumsq_dev})
@@ -154,30 +134,14 @@ void release(mg_eig* s) {
   s->nev = 0;
 }
 
-size_t field_bytes(const mg_eig* s) { return (size_t)s->cs * sizeof(double); }
-
 // host array (nx, ny) of hdt -> fp64 device field with the solver's pitch, on the engine's stream
-int upload(mg_eig* s, double* dev, const void* host, int hdt) {
-  hipStream_t st = s->eng->stream;
-  const size_t es = esize(hdt);
-  if (hdt == MG_F64) {
-    HIPC(&s->err, hipMemcpy2DAsync(dev, (size_t)s->ld * 8, host, (size_t)s->ny * 8, (size_t)s->ny * 8, s->nx, hipMemcpyHostToDevice, st));
-  } else {
-    const int lds = pitch_elems(hdt, s->ny);
-    HIPC(&s->err, hipMemcpy2DAsync(s->staging, (size_t)lds * es, host, (size_t)s->ny * es, (size_t)s->ny * es, s->nx, hipMemcpyHostToDevice, st));
-    d_convert(hdt, MG_F64, s->staging, dev, s->nx, s->ny, lds, s->ld, st);
-  }
-  HIPC(&s->err, hipStreamSynchronize(st));      // the caller's array may go away
-  return MG_OK;
+int put(mg_eig* s, double* dev, const void* host, int hdt) {
+  return upload(&s->err, dev, MG_F64, s->ld, host, hdt, s->nx, s->ny, s->staging, s->eng->stream);
 }
 
 // w = M r: num_cycles cycles from the zero iterate on the engine (the ring of r is zero: mg_update_rhs_device's contract)
 int precondition(mg_eig* s, const double* r, double* w) {
-  if (!s->eng_has_rhs) { ENG(mg_set_rhs_device(s->eng, r, s->ld, MG_F64)); s->eng_has_rhs = true; }
-  else ENG(mg_update_rhs_device(s->eng, r, s->ld, MG_F64));
-  ENG(mg_zero_solution_device(s->eng));
-  ENG(mg_cycle(s->eng, s->num_cycles));
-  ENG(mg_get_solution_device(s->eng, w, s->ld, MG_F64));
+  OWNED(engine_precondition(s->eng, &s->eng_has_rhs, r, w, s->ld, s->num_cycles), "preconditioner: ", mg_last_error(s->eng));
   return MG_OK;
 }
 
@@ -215,7 +179,7 @@ int combine(mg_eig* s, int p, const double* in, int q, const double* coef, doubl
 
 int gram(mg_eig* s, int p, const double* u, int q, const double* v) {
   if (launch_gram(p, u, q, v, s->cs, s->nx, s->ny, s->ld, s->scratch, s->scratch_doubles, s->g_dev, s->eng->stream) != MG_OK)
-    return efail(s, MG_ERR_HIP, "mg_eig: hipFuncSetAttribute failed");
+    return sfail(s, MG_ERR_HIP, "mg_eig: hipFuncSetAttribute failed");
   return fetch(s, s->g_dev, p * q);
 }
 
@@ -232,7 +196,7 @@ int solve(mg_eig* s, int nev, const void* x0, int hdt, double tol, int max_iter,
   int rc;
   for (int b = 0; b < 2; ++b) HIPC(&s->err, hipMemsetAsync(s->blk[b], 0, field_bytes(s) * 6 * m, st));
   for (int i = 0; i < m; ++i)
-    if ((rc = upload(s, s->col(0, kSlotX, i), (const char*)x0 + i * host_col, hdt)) != MG_OK) return rc;
+    if ((rc = put(s, s->col(0, kSlotX, i), (const char*)x0 + i * host_col, hdt)) != MG_OK) return rc;
   hipLaunchKernelGGL(mg::eig_zero_ring_kernel, dim3(std::max(1, std::min(64, (2 * (nx + ny) + mg::kBlock - 1) / mg::kBlock)), 1, m),
                      dim3(mg::kBlock), 0, st, s->col(0, kSlotX), nx, ny, s->ld, s->cs);
 
@@ -240,7 +204,7 @@ int solve(mg_eig* s, int nev, const void* x0, int hdt, double tol, int max_iter,
   // start: X orthonormal in block 1, AX = A X, Rayleigh-Ritz on X^T A X, the rotated pair in block 0
   if ((rc = gram(s, m, s->col(0, kSlotX), m, s->col(0, kSlotX))) != MG_OK) return rc;
   if (!mgd::chol_orth_transform(m, s->h_pin, T))
-    return efail(s, MG_ERR_INVALID_VALUE, "mg_eig_solve: the start vectors are linearly dependent (or not finite) on the interior cells");
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_eig_solve: the start vectors are linearly dependent (or not finite) on the interior cells");
   if ((rc = combine(s, m, s->col(0, kSlotX), m, T, s->col(1, kSlotX))) != MG_OK) return rc;
   apply(s, s->col(1, kSlotX), s->col(1, kSlotAX), m);
   if ((rc = gram(s, m, s->col(1, kSlotX), m, s->col(1, kSlotAX))) != MG_OK) return rc;
@@ -409,8 +373,6 @@ int solve(mg_eig* s, int nev, const void* x0, int hdt, double tol, int max_iter,
 
 }  // namespace
 
-#define CHECK_DEV(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
-
 extern "C" {
 
 int mg_eig_create(const mg_config* cfg, int block_size, int num_cycles, mg_eig** out) {
@@ -434,7 +396,7 @@ int mg_eig_create(const mg_config* cfg, int block_size, int num_cycles, mg_eig**
   s->hx = eng->lv[0].hx; s->hy = eng->lv[0].hy;
   s->m = block_size;
   s->num_cycles = num_cycles;
-  auto bail = [&](int code) { release(s); const std::string msg = s->err; delete s; last_error() = msg; return code; };
+  auto bail = [&](int code) { return create_fail(s, release, code); };
   hipStream_t st = eng->stream;
   for (int b = 0; b < 2; ++b)
     if ((rc = alloc_zero(&s->err, (void**)&s->blk[b], field_bytes(s) * 6 * block_size, st)) != MG_OK) return bail(rc);
@@ -456,23 +418,18 @@ int mg_eig_create(const mg_config* cfg, int block_size, int num_cycles, mg_eig**
 }
 
 int mg_eig_destroy(mg_eig* s) {
-  if (!s) return MG_OK;
-  (void)hipSetDevice(s->cfg.device);
-  if (s->eng && s->eng->stream) (void)hipStreamSynchronize(s->eng->stream);
-  release(s);
-  delete s;
-  return MG_OK;
+  return destroy_owned(s, s && s->eng ? s->eng->stream : nullptr, release);
 }
 
 const char* mg_eig_last_error(const mg_eig* s) { return s ? s->err.c_str() : last_error().c_str(); }
 
 int mg_eig_set_coefficient(mg_eig* s, const void* a_host_or_null, int host_dtype) {
-  if (!s || !valid_dtype(host_dtype)) return efail(s, MG_ERR_INVALID_VALUE, "mg_eig_set_coefficient: bad argument");
+  if (!s || !valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_eig_set_coefficient: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  ENG(mg_set_coefficient(s->eng, a_host_or_null, host_dtype));
+  OWNED(mg_set_coefficient(s->eng, a_host_or_null, host_dtype), "preconditioner: ", mg_last_error(s->eng));
   if (!a_host_or_null) { s->varcoef = false; return MG_OK; }
   if (!s->a) { const int rc = alloc_zero(&s->err, (void**)&s->a, field_bytes(s), s->eng->stream); if (rc != MG_OK) return rc; }
-  const int rc = upload(s, s->a, a_host_or_null, host_dtype);
+  const int rc = put(s, s->a, a_host_or_null, host_dtype);
   if (rc != MG_OK) return rc;
   s->varcoef = true;
   return MG_OK;
@@ -482,9 +439,9 @@ int mg_eig_solve(mg_eig* s, int nev, const void* x0_host, int host_dtype, double
                  void* vectors_out, double* residuals, double* hist, int hist_cap, int* n_iter, int* converged, mg_eig_stats* stats) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_eig_solve: NULL solver");
   if (!x0_host || !eigenvalues || !vectors_out || !residuals || !hist || !n_iter || !converged)
-    return efail(s, MG_ERR_INVALID_VALUE, "mg_eig_solve: NULL argument");
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_eig_solve: NULL argument");
   if (!valid_dtype(host_dtype) || hist_cap < 1 || max_iter < 0 || !(tol == tol) || nev < 1 || nev > s->m)
-    return efail(s, MG_ERR_INVALID_VALUE, "mg_eig_solve: bad dtype / hist_cap < 1 / max_iter < 0 / tol is NaN / nev outside 1 .. block_size");
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_eig_solve: bad dtype / hist_cap < 1 / max_iter < 0 / tol is NaN / nev outside 1 .. block_size");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   const int rc = solve(s, nev, x0_host, host_dtype, tol, max_iter, eigenvalues, vectors_out, residuals, hist, hist_cap, n_iter, converged, stats);
   if (rc != MG_OK) (void)hipStreamSynchronize(s->eng->stream);
@@ -499,9 +456,9 @@ int mg_eig_host_ritz(int n, int m, const double* ga, const double* gb, double* e
 
 int mg_dev_eig_apply(int nx, int ny, int ld, int ncols, int64_t col_stride, double hx, double hy, double coeff, const double* a_or_null,
                      const double* v, double* av, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && ncols >= 1 && ncols <= 65535 && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0,
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && ncols >= 1 && ncols <= 65535 && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0,
             "mg_dev_eig_apply: bad shape / pitch / column count / column stride");
-  CHECK_DEV(v && av && v != av && aligned16(v) && aligned16(av) && aligned16(a_or_null), "mg_dev_eig_apply: NULL, unaligned or aliased pointer");
+  CHECK_ARG(v && av && v != av && aligned16(v) && aligned16(av) && aligned16(a_or_null), "mg_dev_eig_apply: NULL, unaligned or aliased pointer");
   launch_apply(v, av, a_or_null, ncols, col_stride, nx, ny, ld, hx, hy, coeff, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;
@@ -509,9 +466,9 @@ int mg_dev_eig_apply(int nx, int ny, int ld, int ncols, int64_t col_stride, doub
 
 int mg_dev_eig_gram(int nx, int ny, int ld, int64_t col_stride, int p, const double* u, int q, const double* v, void* scratch,
                     double* g_dev, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0, "mg_dev_eig_gram: bad shape / pitch / column stride");
-  CHECK_DEV(p >= 1 && p <= mg::kEigMaxP && q >= 1 && q <= mg::kEigMaxQ, "mg_dev_eig_gram: p outside 1 .. 48 or q outside 1 .. 96");
-  CHECK_DEV(u && v && scratch && g_dev && aligned16(u) && aligned16(v) && aligned16(scratch), "mg_dev_eig_gram: NULL or unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0, "mg_dev_eig_gram: bad shape / pitch / column stride");
+  CHECK_ARG(p >= 1 && p <= mg::kEigMaxP && q >= 1 && q <= mg::kEigMaxQ, "mg_dev_eig_gram: p outside 1 .. 48 or q outside 1 .. 96");
+  CHECK_ARG(u && v && scratch && g_dev && aligned16(u) && aligned16(v) && aligned16(scratch), "mg_dev_eig_gram: NULL or unaligned pointer");
   if (launch_gram(p, u, q, v, col_stride, nx, ny, ld, (double*)scratch, max_partials(nx, ny), g_dev, (hipStream_t)stream) != MG_OK)
     return fail(nullptr, MG_ERR_HIP, "mg_dev_eig_gram: hipFuncSetAttribute failed");
   HIPC(nullptr, hipGetLastError());
@@ -520,10 +477,10 @@ int mg_dev_eig_gram(int nx, int ny, int ld, int64_t col_stride, int p, const dou
 
 int mg_dev_eig_combine(int nx, int ny, int ld, int64_t col_stride, int p, const double* in, int q, const double* coef_dev, double* out,
                        void* stream) {
-  CHECK_DEV(nx >= 1 && ny >= 1 && ld_ok(ny, ld) && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0, "mg_dev_eig_combine: bad shape / pitch / column stride");
-  CHECK_DEV(p >= 1 && p <= mg::kEigMaxP && q >= 1 && q <= mg::kEigMaxQ, "mg_dev_eig_combine: p outside 1 .. 48 or q outside 1 .. 96");
-  CHECK_DEV(in && out && coef_dev && aligned16(in) && aligned16(out), "mg_dev_eig_combine: NULL or unaligned pointer");
-  CHECK_DEV(out + (int64_t)q * col_stride <= in || in + (int64_t)p * col_stride <= out, "mg_dev_eig_combine: out overlaps in");
+  CHECK_ARG(nx >= 1 && ny >= 1 && ld_ok_f64(ny, ld) && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0, "mg_dev_eig_combine: bad shape / pitch / column stride");
+  CHECK_ARG(p >= 1 && p <= mg::kEigMaxP && q >= 1 && q <= mg::kEigMaxQ, "mg_dev_eig_combine: p outside 1 .. 48 or q outside 1 .. 96");
+  CHECK_ARG(in && out && coef_dev && aligned16(in) && aligned16(out), "mg_dev_eig_combine: NULL or unaligned pointer");
+  CHECK_ARG(out + (int64_t)q * col_stride <= in || in + (int64_t)p * col_stride <= out, "mg_dev_eig_combine: out overlaps in");
   launch_combine(p, in, q, coef_dev, out, col_stride, nx, ny, ld, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;
@@ -531,9 +488,9 @@ int mg_dev_eig_combine(int nx, int ny, int ld, int64_t col_stride, int p, const 
 
 int mg_dev_eig_residual(int nx, int ny, int ld, int ncols, int64_t col_stride, const double* x, const double* ax, const double* lambda_dev,
                         double* r, void* scratch, double* sumsq_dev, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && ncols >= 1 && ncols <= kMaxBlock && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0,
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && ncols >= 1 && ncols <= kMaxBlock && col_stride >= (int64_t)nx * ld && col_stride % 2 == 0,
             "mg_dev_eig_residual: bad shape / pitch / column count / column stride");
-  CHECK_DEV(x && ax && lambda_dev && r && scratch && sumsq_dev && r != x && r != ax && aligned16(x) && aligned16(ax) && aligned16(r),
+  CHECK_ARG(x && ax && lambda_dev && r && scratch && sumsq_dev && r != x && r != ax && aligned16(x) && aligned16(ax) && aligned16(r),
             "mg_dev_eig_residual: NULL, unaligned or aliased pointer");
   launch_residual(ncols, x, ax, lambda_dev, r, col_stride, nx, ny, ld, (double*)scratch, max_partials(nx, ny), sumsq_dev, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
@@ -541,7 +498,7 @@ int mg_dev_eig_residual(int nx, int ny, int ld, int ncols, int64_t col_stride, c
 }
 
 int mg_eig_time_op(mg_eig* s, int op, int reps, double* avg_ms) {
-  if (!s || !avg_ms || reps < 1 || op < 0 || op > 3) return efail(s, MG_ERR_INVALID_VALUE, "mg_eig_time_op: bad argument");
+  if (!s || !avg_ms || reps < 1 || op < 0 || op > 3) return sfail(s, MG_ERR_INVALID_VALUE, "mg_eig_time_op: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   hipStream_t st = s->eng->stream;
   const int m = s->m;
@@ -567,7 +524,7 @@ int mg_eig_time_op(mg_eig* s, int op, int reps, double* avg_ms) {
   if (rc == MG_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = MG_ERR_HIP;
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
-  if (rc != MG_OK) return s->err.empty() ? efail(s, rc, "mg_eig_time_op: a HIP call failed") : rc;
+  if (rc != MG_OK) return s->err.empty() ? sfail(s, rc, "mg_eig_time_op: a HIP call failed") : rc;
   *avg_ms = (double)ms / reps;
   return MG_OK;
 }

@@ -14,7 +14,7 @@ std::string& last_error() {
 }
 
 // ------------------------------------------------------------------ host <-> device helpers -----
-static int upload(std::string* err, void* dev, int ddt, int ld, const void* host, int hdt, int nx, int ny, void* staging,
+int upload(std::string* err, void* dev, int ddt, int ld, const void* host, int hdt, int nx, int ny, void* staging,
            hipStream_t st) {
   if (ddt == hdt) {
     HIPC(err, hipMemcpy2DAsync(dev, (size_t)ld * esize(ddt), host, (size_t)ny * esize(hdt), (size_t)ny * esize(hdt), nx,
@@ -616,6 +616,23 @@ int set_u_device_impl(mg_handle* h, const void* u_dev, int ld, int dtype) {
 // (fine_norm and solve_begin in mg_solve.hip test ring_sumsq >= 0); mg_update_rhs_device keeps whatever is recorded.
 // With a zero ring the sum is known to be 0, and mg_iterate runs the loop mg_solve runs after a host upload.
 void rhs_ring_is_zero(mg_handle* h) { h->ring_sumsq[MG_F32] = h->ring_sumsq[MG_F64] = 0.0; }
+
+int engine_set_rhs(mg_handle* eng, bool* has_rhs, const double* f, int ld, bool ring_is_zero) {
+  if (*has_rhs) return mg_update_rhs_device(eng, f, ld, MG_F64);
+  const int rc = mg_set_rhs_device(eng, f, ld, MG_F64);
+  if (rc != MG_OK) return rc;
+  if (ring_is_zero) rhs_ring_is_zero(eng);
+  *has_rhs = true;
+  return MG_OK;
+}
+
+int engine_precondition(mg_handle* eng, bool* has_rhs, const double* r, double* z, int ld, int num_cycles) {
+  int rc = engine_set_rhs(eng, has_rhs, r, ld, false);
+  if (rc == MG_OK) rc = mg_zero_solution_device(eng);
+  if (rc == MG_OK) rc = mg_cycle(eng, num_cycles);
+  if (rc == MG_OK) rc = mg_get_solution_device(eng, z, ld, MG_F64);
+  return rc;
+}
 
 }  // namespace mgh
 

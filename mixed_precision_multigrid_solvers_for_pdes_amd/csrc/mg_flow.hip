@@ -44,31 +44,12 @@ struct mg_flow {
 
 namespace {
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-bool ld_ok(int ny, int ld) { return ld >= ny && ld % 2 == 0; }
-// do the fields a and b (nx rows of pitch ld; b may be NULL) share an element?
-bool overlap(const double* a, const double* b, int nx, int ld) {
-  const uintptr_t n = (uintptr_t)nx * (uintptr_t)ld * sizeof(double), pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return b && pa < pb + n && pb < pa + n;
-}
-
-mg::TileGeom flow_geom(int nx, int ny, int ld) {
-  using S = mg::TileShape<double>;
-  mg::TileGeom g;
-  g.nx = nx; g.ny = ny; g.ld = ld;
-  g.nyv = std::min(ld, (ny + S::N - 1) / S::N * S::N);
-  g.i_org = 0;                                             // the ring rows are stored too
-  g.tiles_j = (ny + S::TJ - 1) / S::TJ;
-  g.ntiles = (nx + mg::kTI - 1) / mg::kTI * g.tiles_j;
-  return g;
-}
-
 // ---- launchers (shared by the driver and the stateless mg_dev_flow_* forms); an int result is the number of partials per
 // result ----
 int launch_rhs(int nx, int ny, int ld, double hx, double hy, double nu, double dt, double c0, double c1, const double* psi,
                const double* w, const double* n_prev, const double* force, double* f_out, double* n_out, double* partials,
                hipStream_t st) {
-  const mg::TileGeom g = flow_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const Coef k = coefs(hx, hy);
   mg::FlowCoef c;
   c.ihx2 = k.ihx2; c.ihy2 = k.ihy2; c.diag = k.diag;
@@ -91,7 +72,7 @@ void launch_wall(double* w, const double* psi, int nx, int ny, int ld, double hx
 int stream_blocks(long long vecs) { return (int)std::max<long long>(1, std::min<long long>((vecs + mg::kBlock - 1) / mg::kBlock, 512)); }
 
 int launch_interior(const double* w, const double* w_old, double* out, double* partials, int nx, int ny, int ld, hipStream_t st) {
-  const int nyv = flow_geom(nx, ny, ld).nyv;
+  const int nyv = field_geom(nx, ny, ld).nyv;
   const int nb = stream_blocks((long long)nx * (nyv / 2));
   auto kern = w_old ? mg::flow_interior_kernel<true> : mg::flow_interior_kernel<false>;
   hipLaunchKernelGGL(kern, dim3(nb), dim3(mg::kBlock), 0, st, w, w_old, out, partials, nx, ny, nyv, ld);
@@ -99,7 +80,7 @@ int launch_interior(const double* w, const double* w_old, double* out, double* p
 }
 
 int launch_diag(const double* psi, const double* w, double* partials, int nx, int ny, int ld, hipStream_t st) {
-  const int nyv = flow_geom(nx, ny, ld).nyv;
+  const int nyv = field_geom(nx, ny, ld).nyv;
   const int nb = stream_blocks((long long)(nx - 2) * (nyv / 2));
   hipLaunchKernelGGL(mg::flow_diag_kernel, dim3(nb), dim3(mg::kBlock), 0, st, psi, w, partials, nx, ny, nyv, ld);
   return nb;
@@ -110,15 +91,6 @@ void launch_reduce_results(const double* partials, int n, int results, int max_m
   hipLaunchKernelGGL(mg::flow_reduce_kernel, dim3(results), dim3(mg::kReduceBlock), 0, st, partials, n, max_mask, out);
 }
 
-int ffail(mg_flow* s, int code, const std::string& msg) { return fail(s ? &s->err : nullptr, code, msg); }
-
-// an engine's message joins the stepper's
-int eng_rc(mg_flow* s, mg_handle* e, int rc) {
-  if (rc != MG_OK) ffail(s, rc, std::string("inner solver: ") + mg_last_error(e));
-  return rc;
-}
-#define ENG(e, call) do { const int rc_ = eng_rc(s, (e), (call)); if (rc_ != MG_OK) return rc_; } while (0)
-
 void release(mg_flow* s) {
   if (s->eng_w) { (void)mg_destroy(s->eng_w); s->eng_w = nullptr; }          // first: it runs on the other engine's stream
   if (s->eng_psi) { (void)mg_destroy(s->eng_psi); s->eng_psi = nullptr; }
@@ -127,7 +99,6 @@ void release(mg_flow* s) {
   if (s->h_sc) { (void)hipHostFree(s->h_sc); s->h_sc = nullptr; }
 }
 
-size_t field_bytes(const mg_flow* s) { return (size_t)s->nx * s->ld * sizeof(double); }
 hipStream_t stream_of(const mg_flow* s) { return s->eng_psi->stream; }
 
 double* field_of(mg_flow* s, int which) {
@@ -135,21 +106,8 @@ double* field_of(mg_flow* s, int which) {
 }
 
 // host array (nx, ny) of hdt -> fp64 device field with the stepper's pitch, on the stepper's stream (through the staging field)
-int upload(mg_flow* s, double* dev, const void* host, int hdt) {
-  hipStream_t st = stream_of(s);
-  const size_t es = esize(hdt);
-  if (hdt == MG_F64) {
-    HIPC(&s->err, hipMemcpy2DAsync(dev, (size_t)s->ld * 8, host, (size_t)s->ny * 8, (size_t)s->ny * 8, s->nx, hipMemcpyHostToDevice, st));
-  } else {
-    int lds = 0;
-    (void)mg_pitch_elems(hdt, s->ny, &lds);
-    void* staging = s->eng_psi->staging;
-    HIPC(&s->err, hipMemcpy2DAsync(staging, (size_t)lds * es, host, (size_t)s->ny * es, (size_t)s->ny * es, s->nx, hipMemcpyHostToDevice, st));
-    const int rc = mg_dev_convert(hdt, MG_F64, s->nx, s->ny, lds, s->ld, staging, dev, st);
-    if (rc != MG_OK) return ffail(s, rc, mg_last_error(nullptr));
-  }
-  HIPC(&s->err, hipStreamSynchronize(st));      // the caller's array may go away
-  return MG_OK;
+int put(mg_flow* s, double* dev, const void* host, int hdt) {
+  return upload(&s->err, dev, MG_F64, s->ld, host, hdt, s->nx, s->ny, s->eng_psi->staging, stream_of(s));
 }
 
 bool all_finite(const void* host, int hdt, size_t n) {
@@ -169,14 +127,9 @@ struct SolveOut {
 int solve_on(mg_flow* s, mg_handle* eng, bool* has_rhs, const double* guess, double* dst, int slot, double tol, int max_cycles,
              double* fnorm_out, SolveOut* out) {
   hipStream_t st = stream_of(s);
-  if (!*has_rhs) {
-    ENG(eng, mg_set_rhs_device(eng, s->f, s->ld, MG_F64));
-    rhs_ring_is_zero(eng);      // f has a zero ring by construction: mg_iterate runs the loop mg_solve runs after an upload
-    *has_rhs = true;
-  } else {
-    ENG(eng, mg_update_rhs_device(eng, s->f, s->ld, MG_F64));
-  }
-  ENG(eng, set_u_device_impl(eng, guess, s->ld, MG_F64));
+  // f has a zero ring by construction: mg_iterate runs the loop mg_solve runs after an upload
+  OWNED(engine_set_rhs(eng, has_rhs, s->f, s->ld, true), "inner solver: ", mg_last_error(eng));
+  OWNED(set_u_device_impl(eng, guess, s->ld, MG_F64), "inner solver: ", mg_last_error(eng));
   HIPC(&s->err, hipStreamSynchronize(st));                        // the scalars have arrived
   const double fnorm = std::sqrt(s->hx * s->hy * s->h_sc[slot]);
   if ((int)s->hist.size() < max_cycles) s->hist.resize(max_cycles);
@@ -185,8 +138,8 @@ int solve_on(mg_flow* s, mg_handle* eng, bool* has_rhs, const double* guess, dou
   // A NaN norm: std::max(1.0, NaN) is 1.0, so the target is `tol` and no NaN residual is below it -- the solve runs to its
   // cap and reports converged = 0; the NaN itself is visible to the caller in rhs_norm.
 
-  ENG(eng, mg_iterate(eng, tol * std::max(1.0, fnorm), max_cycles, s->hist.data(), max_cycles, &n, &conv, nullptr, &stats));
-  ENG(eng, mg_get_solution_device(eng, dst, s->ld, MG_F64));
+  OWNED(mg_iterate(eng, tol * std::max(1.0, fnorm), max_cycles, s->hist.data(), max_cycles, &n, &conv, nullptr, &stats), "inner solver: ", mg_last_error(eng));
+  OWNED(mg_get_solution_device(eng, dst, s->ld, MG_F64), "inner solver: ", mg_last_error(eng));
   *fnorm_out = fnorm;
   out->initial = stats.initial_residual;
   out->final = n > 0 ? s->hist[n - 1] : stats.initial_residual;
@@ -219,8 +172,6 @@ int psi_solve(mg_flow* s, const double* w_src, const double* w_old, double tol, 
 
 }  // namespace
 
-#define CHECK_DEV(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
-
 extern "C" {
 
 int mg_flow_create(const mg_config* cfg, double nu, int wall_kind, mg_flow** out) {
@@ -245,7 +196,7 @@ int mg_flow_create(const mg_config* cfg, double nu, int wall_kind, mg_flow** out
   s->hx = ep->lv[0].hx; s->hy = ep->lv[0].hy;
   s->nu = nu;
   s->wall = wall_kind;
-  auto bail = [&](int code) { release(s); const std::string m = s->err; delete s; last_error() = m; return code; };
+  auto bail = [&](int code) { return create_fail(s, release, code); };
   if ((rc = mg_set_stream(ew, ep->stream, 0)) != MG_OK) { s->err = mg_last_error(ew); return bail(rc); }      // one stream for everything
   hipStream_t st = ep->stream;
   for (double** p : {&s->w, &s->w_new, &s->psi, &s->n_cur, &s->n_new, &s->f})
@@ -273,17 +224,17 @@ int mg_flow_destroy(mg_flow* s) {
 const char* mg_flow_last_error(const mg_flow* s) { return s ? s->err.c_str() : last_error().c_str(); }
 
 int mg_flow_set_walls(mg_flow* s, const double* speeds4) {
-  if (!s || !speeds4) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_walls: bad argument");
+  if (!s || !speeds4) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_walls: bad argument");
   for (int k = 0; k < 4; ++k)
-    if (!std::isfinite(speeds4[k])) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_walls: wall speeds must be finite");
+    if (!std::isfinite(speeds4[k])) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_walls: wall speeds must be finite");
   for (int k = 0; k < 4; ++k) s->speeds[k] = speeds4[k];
   return MG_OK;
 }
 
 int mg_flow_set_forcing(mg_flow* s, const void* f_host_or_null, int host_dtype) {
-  if (!s || !valid_dtype(host_dtype)) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_forcing: bad argument");
+  if (!s || !valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_forcing: bad argument");
   if (f_host_or_null && !all_finite(f_host_or_null, host_dtype, (size_t)s->nx * s->ny))          // before any device work
-    return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_forcing: the forcing field must be finite everywhere");
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_forcing: the forcing field must be finite everywhere");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   if (!f_host_or_null) {
     HIPC(&s->err, hipStreamSynchronize(stream_of(s)));
@@ -291,18 +242,18 @@ int mg_flow_set_forcing(mg_flow* s, const void* f_host_or_null, int host_dtype) 
     return MG_OK;
   }
   if (!s->force) { const int rc = alloc_zero(&s->err, (void**)&s->force, field_bytes(s), stream_of(s)); if (rc != MG_OK) return rc; }
-  return upload(s, s->force, f_host_or_null, host_dtype);
+  return put(s, s->force, f_host_or_null, host_dtype);
 }
 
 int mg_flow_set_state(mg_flow* s, const void* omega_host, int host_dtype, double tol, int max_cycles, mg_flow_step_info* info) {
-  if (!s || !omega_host || !valid_dtype(host_dtype)) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_state: bad argument");
-  if (max_cycles < 1 || !(tol == tol)) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_state: max_cycles < 1 / tol is NaN");
+  if (!s || !omega_host || !valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_state: bad argument");
+  if (max_cycles < 1 || !(tol == tol)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_state: max_cycles < 1 / tol is NaN");
   if (!all_finite(omega_host, host_dtype, (size_t)s->nx * s->ny))
-    return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_state: the vorticity must be finite everywhere");
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_state: the vorticity must be finite everywhere");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   const double t0 = now_s();
   hipStream_t st = stream_of(s);
-  int rc = upload(s, s->w, omega_host, host_dtype);
+  int rc = put(s, s->w, omega_host, host_dtype);
   if (rc != MG_OK) return rc;
   HIPC(&s->err, hipMemsetAsync(s->psi, 0, field_bytes(s), st));
   if (info) *info = mg_flow_step_info{};
@@ -316,33 +267,31 @@ int mg_flow_set_state(mg_flow* s, const void* omega_host, int host_dtype, double
 }
 
 int mg_flow_get(mg_flow* s, int which, void* host, int host_dtype) {
-  if (!s || !host || !valid_dtype(host_dtype) || !field_of(s, which)) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_get: bad argument");
+  if (!s || !host || !valid_dtype(host_dtype) || !field_of(s, which)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_get: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   return download(&s->err, host, host_dtype, field_of(s, which), MG_F64, s->ld, s->nx, s->ny, s->eng_psi->staging, stream_of(s));
 }
 
 int mg_flow_get_device(mg_flow* s, int which, void* u_dev, int ld, int dtype) {
-  if (!s || !u_dev || !valid_dtype(dtype) || !field_of(s, which) || ld < s->ny) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_get_device: bad argument");
+  if (!s || !u_dev || !valid_dtype(dtype) || !field_of(s, which) || ld < s->ny) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_get_device: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  const int rc = mg_dev_convert(MG_F64, dtype, s->nx, s->ny, s->ld, ld, field_of(s, which), u_dev, stream_of(s));
-  if (rc != MG_OK) return ffail(s, rc, mg_last_error(nullptr));
+  OWNED(mg_dev_convert(MG_F64, dtype, s->nx, s->ny, s->ld, ld, field_of(s, which), u_dev, stream_of(s)), "", mg_last_error(nullptr));
   HIPC(&s->err, hipStreamSynchronize(stream_of(s)));
   return MG_OK;
 }
 
 int mg_flow_set_device(mg_flow* s, int which, const void* u_dev, int ld, int dtype) {
-  if (!s || !u_dev || !valid_dtype(dtype) || !field_of(s, which) || ld < s->ny) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_device: bad argument");
+  if (!s || !u_dev || !valid_dtype(dtype) || !field_of(s, which) || ld < s->ny) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_set_device: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  const int rc = mg_dev_convert(dtype, MG_F64, s->nx, s->ny, ld, s->ld, u_dev, field_of(s, which), stream_of(s));
-  if (rc != MG_OK) return ffail(s, rc, mg_last_error(nullptr));
+  OWNED(mg_dev_convert(dtype, MG_F64, s->nx, s->ny, ld, s->ld, u_dev, field_of(s, which), stream_of(s)), "", mg_last_error(nullptr));
   HIPC(&s->err, hipStreamSynchronize(stream_of(s)));
   return MG_OK;
 }
 
 int mg_flow_step(mg_flow* s, double dt, double tol, int max_cycles, mg_flow_step_info* info) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_flow_step: NULL stepper");
-  if (!(dt > 0.0) || !std::isfinite(dt)) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_step: dt must be finite and > 0");
-  if (max_cycles < 1 || !(tol == tol)) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_step: max_cycles < 1 / tol is NaN");
+  if (!(dt > 0.0) || !std::isfinite(dt)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_step: dt must be finite and > 0");
+  if (max_cycles < 1 || !(tol == tol)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_step: max_cycles < 1 / tol is NaN");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   const double t0 = now_s();
   hipStream_t st = stream_of(s);
@@ -358,7 +307,7 @@ int mg_flow_step(mg_flow* s, double dt, double tol, int max_cycles, mg_flow_step
   launch_reduce_results(s->partials, np, 2, 2, s->d_sc, st);
   HIPC(&s->err, hipGetLastError());
   HIPC(&s->err, hipMemcpyAsync(s->h_sc, s->d_sc, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (sigma != s->sigma) { ENG(s->eng_w, mg_set_shift(s->eng_w, sigma)); s->sigma = sigma; }
+  if (sigma != s->sigma) { OWNED(mg_set_shift(s->eng_w, sigma), "inner solver: ", mg_last_error(s->eng_w)); s->sigma = sigma; }
   // the Dirichlet data of the w solve: the wall values of psi^n, in place (f has been formed from the old ring)
   launch_wall(s->w, s->psi, s->nx, s->ny, s->ld, s->hx, s->hy, s->wall, s->speeds, st);
   HIPC(&s->err, hipGetLastError());
@@ -387,7 +336,7 @@ int mg_flow_step(mg_flow* s, double dt, double tol, int max_cycles, mg_flow_step
 }
 
 int mg_flow_diagnostics(mg_flow* s, double out[2]) {
-  if (!s || !out) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_diagnostics: bad argument");
+  if (!s || !out) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_diagnostics: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   hipStream_t st = stream_of(s);
   const int np = launch_diag(s->psi, s->w, s->partials, s->nx, s->ny, s->ld, st);
@@ -401,7 +350,7 @@ int mg_flow_diagnostics(mg_flow* s, double out[2]) {
 }
 
 int mg_flow_velocity_max(mg_flow* s, double* m) {
-  if (!s || !m) return ffail(s, MG_ERR_INVALID_VALUE, "mg_flow_velocity_max: bad argument");
+  if (!s || !m) return sfail(s, MG_ERR_INVALID_VALUE, "mg_flow_velocity_max: bad argument");
   double two[2];
   const int rc = mg_flow_diagnostics(s, two);
   if (rc != MG_OK) return rc;
@@ -413,16 +362,16 @@ int mg_flow_velocity_max(mg_flow* s, double* m) {
 int mg_dev_flow_rhs(int nx, int ny, int ld, double hx, double hy, double nu, double dt, double c0, double c1, const double* psi,
                     const double* omega, const double* n_prev_or_null, const double* force_or_null, double* f_out, double* n_out,
                     void* scratch, double* out2_dev_or_null, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_flow_rhs: bad shape / pitch");
-  CHECK_DEV(dt > 0.0 && std::isfinite(dt) && nu > 0.0 && std::isfinite(nu) && hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy),
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_flow_rhs: bad shape / pitch");
+  CHECK_ARG(dt > 0.0 && std::isfinite(dt) && nu > 0.0 && std::isfinite(nu) && hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy),
             "mg_dev_flow_rhs: dt, nu and the spacings must be finite and > 0");
-  CHECK_DEV(std::isfinite(c0) && std::isfinite(c1), "mg_dev_flow_rhs: c0 / c1 not finite");
-  CHECK_DEV(psi && omega && f_out && n_out && scratch, "mg_dev_flow_rhs: NULL pointer");
+  CHECK_ARG(std::isfinite(c0) && std::isfinite(c1), "mg_dev_flow_rhs: c0 / c1 not finite");
+  CHECK_ARG(psi && omega && f_out && n_out && scratch, "mg_dev_flow_rhs: NULL pointer");
   for (const double* o : {(const double*)f_out, (const double*)n_out})
-    CHECK_DEV(!overlap(o, psi, nx, ld) && !overlap(o, omega, nx, ld) && !overlap(o, n_prev_or_null, nx, ld) &&
+    CHECK_ARG(!overlap(o, psi, nx, ld) && !overlap(o, omega, nx, ld) && !overlap(o, n_prev_or_null, nx, ld) &&
               !overlap(o, force_or_null, nx, ld), "mg_dev_flow_rhs: an output is an array of its own (it overlaps an input)");
-  CHECK_DEV(!overlap(f_out, n_out, nx, ld), "mg_dev_flow_rhs: an output is an array of its own (f and N overlap)");
-  CHECK_DEV(aligned16(psi) && aligned16(omega) && aligned16(n_prev_or_null) && aligned16(force_or_null) && aligned16(f_out) &&
+  CHECK_ARG(!overlap(f_out, n_out, nx, ld), "mg_dev_flow_rhs: an output is an array of its own (f and N overlap)");
+  CHECK_ARG(aligned16(psi) && aligned16(omega) && aligned16(n_prev_or_null) && aligned16(force_or_null) && aligned16(f_out) &&
             aligned16(n_out), "mg_dev_flow_rhs: unaligned pointer");
   const int n = launch_rhs(nx, ny, ld, hx, hy, nu, dt, c0, c1, psi, omega, n_prev_or_null, force_or_null, f_out, n_out,
                            (double*)scratch, (hipStream_t)stream);
@@ -433,20 +382,20 @@ int mg_dev_flow_rhs(int nx, int ny, int ld, double hx, double hy, double nu, dou
 
 int mg_dev_flow_wall(int nx, int ny, int ld, double hx, double hy, int wall_kind, const double* speeds4, const double* psi,
                      double* omega, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_flow_wall: bad shape / pitch");
-  CHECK_DEV(hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy), "mg_dev_flow_wall: the spacings must be finite and > 0");
-  CHECK_DEV(wall_kind == MG_FLOW_FREE_SLIP || wall_kind == MG_FLOW_NO_SLIP, "mg_dev_flow_wall: unknown wall kind");
-  CHECK_DEV(speeds4 && psi && omega, "mg_dev_flow_wall: NULL pointer");
-  CHECK_DEV(!overlap(omega, psi, nx, ld), "mg_dev_flow_wall: omega and psi overlap");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_flow_wall: bad shape / pitch");
+  CHECK_ARG(hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy), "mg_dev_flow_wall: the spacings must be finite and > 0");
+  CHECK_ARG(wall_kind == MG_FLOW_FREE_SLIP || wall_kind == MG_FLOW_NO_SLIP, "mg_dev_flow_wall: unknown wall kind");
+  CHECK_ARG(speeds4 && psi && omega, "mg_dev_flow_wall: NULL pointer");
+  CHECK_ARG(!overlap(omega, psi, nx, ld), "mg_dev_flow_wall: omega and psi overlap");
   launch_wall(omega, psi, nx, ny, ld, hx, hy, wall_kind, speeds4, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;
 }
 
 int mg_dev_flow_diag(int nx, int ny, int ld, const double* psi, const double* omega, void* scratch, double* out3_dev, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_flow_diag: bad shape / pitch");
-  CHECK_DEV(psi && omega && scratch && out3_dev, "mg_dev_flow_diag: NULL pointer");
-  CHECK_DEV(aligned16(psi) && aligned16(omega), "mg_dev_flow_diag: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_flow_diag: bad shape / pitch");
+  CHECK_ARG(psi && omega && scratch && out3_dev, "mg_dev_flow_diag: NULL pointer");
+  CHECK_ARG(aligned16(psi) && aligned16(omega), "mg_dev_flow_diag: unaligned pointer");
   const int n = launch_diag(psi, omega, (double*)scratch, nx, ny, ld, (hipStream_t)stream);
   launch_reduce_results((double*)scratch, n, 3, 4, out3_dev, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
@@ -455,10 +404,10 @@ int mg_dev_flow_diag(int nx, int ny, int ld, const double* psi, const double* om
 
 int mg_dev_flow_interior(int nx, int ny, int ld, const double* w, const double* w_old_or_null, double* out, void* scratch,
                          double* out2_dev_or_null, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_flow_interior: bad shape / pitch");
-  CHECK_DEV(w && out && scratch, "mg_dev_flow_interior: NULL pointer");
-  CHECK_DEV(!overlap(out, w, nx, ld) && !overlap(out, w_old_or_null, nx, ld), "mg_dev_flow_interior: out is an array of its own (it overlaps an input)");
-  CHECK_DEV(aligned16(w) && aligned16(w_old_or_null) && aligned16(out), "mg_dev_flow_interior: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_flow_interior: bad shape / pitch");
+  CHECK_ARG(w && out && scratch, "mg_dev_flow_interior: NULL pointer");
+  CHECK_ARG(!overlap(out, w, nx, ld) && !overlap(out, w_old_or_null, nx, ld), "mg_dev_flow_interior: out is an array of its own (it overlaps an input)");
+  CHECK_ARG(aligned16(w) && aligned16(w_old_or_null) && aligned16(out), "mg_dev_flow_interior: unaligned pointer");
   const int n = launch_interior(w, w_old_or_null, out, (double*)scratch, nx, ny, ld, (hipStream_t)stream);
   if (out2_dev_or_null) launch_reduce_results((double*)scratch, n, 2, 2, out2_dev_or_null, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());

@@ -11,17 +11,6 @@
 namespace mgh {
 namespace {
 
-mg::TileGeom ho_geom(int nx, int ny, int ld) {
-  using S = mg::TileShape<double>;
-  mg::TileGeom g;
-  g.nx = nx; g.ny = ny; g.ld = ld;
-  g.nyv = std::min(ld, (ny + S::N - 1) / S::N * S::N);
-  g.i_org = 0;
-  g.tiles_j = (ny + S::TJ - 1) / S::TJ;
-  g.ntiles = (nx + mg::kTI - 1) / mg::kTI * g.tiles_j;
-  return g;
-}
-
 // the stencil weights, in exactly the forms include/mghip_ho.h states (the NumPy restatement computes the same bits)
 mg::HoArgs ho_args(double hx, double hy, double coeff, double sigma) {
   const double ca = 1.0 / (hx * hx), cb = 1.0 / (hy * hy);
@@ -38,7 +27,7 @@ mg::HoArgs ho_args(double hx, double hy, double coeff, double sigma) {
 
 int d_ho_direction(const double* z, const double* p_in, double* p_out, double* q, const double* beta, double* partials, int nx,
                    int ny, int ld, double hx, double hy, double coeff, double sigma, hipStream_t st) {
-  const mg::TileGeom g = ho_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   hipLaunchKernelGGL(mg::ho_direction_kernel, dim3(g.ntiles), dim3(mg::kBlock), 0, st, z, p_in, p_out, q, beta, partials, g,
                      ho_args(hx, hy, coeff, sigma));
   return g.ntiles;
@@ -46,14 +35,14 @@ int d_ho_direction(const double* z, const double* p_in, double* p_out, double* q
 
 int d_ho_residual(const double* x, const double* g_rhs, double* r, double* partials, int nx, int ny, int ld, double hx, double hy,
                   double coeff, double sigma, hipStream_t st) {
-  const mg::TileGeom g = ho_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   auto k = r ? mg::ho_residual_kernel<true> : mg::ho_residual_kernel<false>;
   hipLaunchKernelGGL(k, dim3(g.ntiles), dim3(mg::kBlock), 0, st, x, g_rhs, r, partials, g, ho_args(hx, hy, coeff, sigma));
   return g.ntiles;
 }
 
 void d_ho_rhs(const double* f, double* out, int nx, int ny, int ld, hipStream_t st) {
-  const mg::TileGeom g = ho_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   hipLaunchKernelGGL(mg::ho_rhs_kernel, dim3(g.ntiles), dim3(mg::kBlock), 0, st, f, out, g);
 }
 
@@ -61,22 +50,16 @@ void d_ho_rhs(const double* f, double* out, int nx, int ny, int ld, hipStream_t 
 
 using namespace mgh;
 
-#define CHECK_HO(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
-static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-static bool ld_ok(int ny, int ld) { return ld >= ny && ld % 2 == 0; }
-static bool operator_ok(double hx, double hy, double coeff, double sigma) {
-  return hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy) && std::isfinite(coeff) && sigma >= 0.0 && std::isfinite(sigma);
-}
 
 extern "C" {
 
 int mg_dev_ho_direction(int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, const double* z,
                         const double* p_in_or_null, double* p_out, double* q, const double* beta_dev_or_null, void* scratch,
                         double* pq_dev, void* stream) {
-  CHECK_HO(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && operator_ok(hx, hy, coeff, sigma), "mg_dev_ho_direction: bad shape / pitch / spacing / shift");
-  CHECK_HO(z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_ho_direction: NULL pointer");
-  CHECK_HO(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null, "mg_dev_ho_direction: p_out and q are arrays of their own");
-  CHECK_HO(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(scratch), "mg_dev_ho_direction: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && operator_ok(hx, hy, coeff, sigma), "mg_dev_ho_direction: bad shape / pitch / spacing / shift");
+  CHECK_ARG(z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_ho_direction: NULL pointer");
+  CHECK_ARG(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null, "mg_dev_ho_direction: p_out and q are arrays of their own");
+  CHECK_ARG(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(scratch), "mg_dev_ho_direction: unaligned pointer");
   const int n = d_ho_direction(z, beta_dev_or_null ? p_in_or_null : nullptr, p_out, q, beta_dev_or_null, (double*)scratch, nx, ny, ld,
                                hx, hy, coeff, sigma, (hipStream_t)stream);
   launch_reduce((double*)scratch, n, pq_dev, (hipStream_t)stream);
@@ -86,10 +69,10 @@ int mg_dev_ho_direction(int nx, int ny, int ld, double hx, double hy, double coe
 
 int mg_dev_ho_residual(int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, const double* x, const double* g,
                        double* r, void* scratch, double* rr_dev, void* stream) {
-  CHECK_HO(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && operator_ok(hx, hy, coeff, sigma), "mg_dev_ho_residual: bad shape / pitch / spacing / shift");
-  CHECK_HO(x && g && r && scratch && rr_dev, "mg_dev_ho_residual: NULL pointer");
-  CHECK_HO(r != x && r != g, "mg_dev_ho_residual: r is an array of its own");
-  CHECK_HO(aligned16(x) && aligned16(g) && aligned16(r) && aligned16(scratch), "mg_dev_ho_residual: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && operator_ok(hx, hy, coeff, sigma), "mg_dev_ho_residual: bad shape / pitch / spacing / shift");
+  CHECK_ARG(x && g && r && scratch && rr_dev, "mg_dev_ho_residual: NULL pointer");
+  CHECK_ARG(r != x && r != g, "mg_dev_ho_residual: r is an array of its own");
+  CHECK_ARG(aligned16(x) && aligned16(g) && aligned16(r) && aligned16(scratch), "mg_dev_ho_residual: unaligned pointer");
   const int n = d_ho_residual(x, g, r, (double*)scratch, nx, ny, ld, hx, hy, coeff, sigma, (hipStream_t)stream);
   launch_reduce((double*)scratch, n, rr_dev, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
@@ -97,9 +80,9 @@ int mg_dev_ho_residual(int nx, int ny, int ld, double hx, double hy, double coef
 }
 
 int mg_dev_ho_rhs(int nx, int ny, int ld, const double* f, double* g, void* stream) {
-  CHECK_HO(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_ho_rhs: bad shape / pitch");
-  CHECK_HO(f && g && f != g, "mg_dev_ho_rhs: NULL pointer, or g is not an array of its own");
-  CHECK_HO(aligned16(f) && aligned16(g), "mg_dev_ho_rhs: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_ho_rhs: bad shape / pitch");
+  CHECK_ARG(f && g && f != g, "mg_dev_ho_rhs: NULL pointer, or g is not an array of its own");
+  CHECK_ARG(aligned16(f) && aligned16(g), "mg_dev_ho_rhs: unaligned pointer");
   d_ho_rhs(f, g, nx, ny, ld, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;
@@ -136,12 +119,12 @@ static int ho_host(bool apply, int nx, int ny, double hx, double hy, double coef
 }
 
 int mg_op_apply_ho(int nx, int ny, double hx, double hy, double coeff, double sigma, const double* u, double* out) {
-  CHECK_HO(nx >= 3 && ny >= 3 && u && out && operator_ok(hx, hy, coeff, sigma), "mg_op_apply_ho: bad argument");
+  CHECK_ARG(nx >= 3 && ny >= 3 && u && out && operator_ok(hx, hy, coeff, sigma), "mg_op_apply_ho: bad argument");
   return ho_host(true, nx, ny, hx, hy, coeff, sigma, u, out);
 }
 
 int mg_op_rhs_ho(int nx, int ny, const double* f, double* g) {
-  CHECK_HO(nx >= 3 && ny >= 3 && f && g, "mg_op_rhs_ho: bad argument");
+  CHECK_ARG(nx >= 3 && ny >= 3 && f && g, "mg_op_rhs_ho: bad argument");
   return ho_host(false, nx, ny, 1.0, 1.0, -1.0, 0.0, f, g);
 }
 

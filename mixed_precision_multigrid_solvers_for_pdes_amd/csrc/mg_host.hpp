@@ -1,7 +1,12 @@
 // Host-side types and helpers shared by the translation units of libmghip.so (mg_launch.hip: the kernel launchers;
 // mg_engine.hip: the handle and the cycle driver; mg_solve.hip: norms, precision policy and the solve loop; mg_dev.hip: the
-// stateless C ABI; mg_tail.hip: the register-resident coarse tail).  Internal: nothing here is part of the C ABI
-// (include/mghip.h).
+// stateless C ABI; mg_tail.hip: the register-resident coarse tail) and by the solver units on top of the engine (mg_pcg,
+// mg_heat, mg_eig, mg_ho, mg_flow, mg_nl, mg_rd, mg_line).  What those units would otherwise each define lives here, once:
+// the argument predicates and CHECK_ARG of the stateless device forms, the whole-field tile geometry (field_geom), the error
+// plumbing of an object that owns an engine or another solver (sfail, OWNED), its create / destroy boilerplate (create_fail,
+// destroy_owned) and, declared here and defined in mg_engine.hip, the host transfers (upload, download) and the hand-over of
+// a right-hand side to an engine (engine_set_rhs, engine_precondition).  Launch shapes and their caps stay in the units.
+// Internal: nothing here is part of the C ABI (include/mghip.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <string>
 #include <type_traits>
@@ -45,6 +51,75 @@ inline double now_s() {
 
 inline size_t esize(int dt) { return dt == MG_F32 ? 4 : 8; }
 inline bool valid_dtype(int dt) { return dt == MG_F32 || dt == MG_F64; }
+
+// ---- what the solver units and the stateless device forms share ----
+// an argument check of a stateless form (no object to keep the message: the thread's last error gets it)
+#define CHECK_ARG(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
+// a failure of a solver object (nullable): the message goes to the object and to the thread
+template <class S> int sfail(S* s, int code, const std::string& msg) { return fail(s ? &s->err : nullptr, code, msg); }
+// a call into an object that `s` owns (an engine, an mg_pcg, an mg_nl) or into a stateless form of another unit: when it
+// fails, its message (`owner_msg`, read after the call) joins s's under `prefix` and the calling function returns its code
+#define OWNED(call, prefix, owner_msg) \
+  do { const int rc_ = (call); if (rc_ != MG_OK) return sfail(s, rc_, std::string(prefix) + (owner_msg)); } while (0)
+// a *_create that fails after the object exists: free what it holds, and leave its message as the thread's
+template <class S> int create_fail(S* s, void (*release)(S*), int code) {
+  release(s);
+  const std::string m = s->err;
+  delete s;
+  last_error() = m;
+  return code;
+}
+// *_destroy: wait for the stream that carries the object's work (NULL: none), then free what it holds
+template <class S> int destroy_owned(S* s, hipStream_t st, void (*release)(S*)) {
+  if (!s) return MG_OK;
+  (void)hipSetDevice(s->cfg.device);
+  if (st) (void)hipStreamSynchronize(st);
+  release(s);
+  delete s;
+  return MG_OK;
+}
+
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// pitch of an fp64 field: whole 16-byte vectors per row (mg_dev.hip has the dtype-aware rule)
+inline bool ld_ok_f64(int ny, int ld) { return ld >= ny && ld % 2 == 0; }
+// do the fp64 fields a and b (nx rows of pitch ld; b may be NULL) share an element?
+inline bool overlap(const double* a, const double* b, int nx, int ld) {
+  const uintptr_t n = (uintptr_t)nx * (uintptr_t)ld * sizeof(double), pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return b && pa < pb + n && pb < pa + n;
+}
+inline bool pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
+inline bool operator_ok(double hx, double hy, double coeff, double sigma) {
+  return hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy) && std::isfinite(coeff) && sigma >= 0.0 && std::isfinite(sigma);
+}
+// a nonlinearity of include/mghip_nl.h, which this header does not see: the caller names the first and the last kind
+inline bool kind_ok(int kind, int first, int last) { return kind >= first && kind <= last; }
+inline bool kappa_ok(double kappa) { return kappa >= 0.0 && std::isfinite(kappa); }
+// every entry of a host field finite and >= 0 (a weight) / > 0 (a diffusivity)
+template <typename T> bool weight_ok(const T* w, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    if (!(w[k] >= T(0)) || !std::isfinite((double)w[k])) return false;
+  return true;
+}
+template <typename T> bool coefficient_ok(const T* a, size_t n) {
+  for (size_t k = 0; k < n; ++k)
+    if (!(a[k] > T(0)) || !std::isfinite((double)a[k])) return false;
+  return true;
+}
+
+// bytes of one fp64 field of a solver object
+template <class S> size_t field_bytes(const S* s) { return (size_t)s->nx * s->ld * sizeof(double); }
+// The tile geometry of a whole fp64 field, ring rows included (i_org = 0): what every LDS-tiled kernel of the solver units
+// is launched over, one workgroup per tile.  (The engine's smoothers tile the interior alone: make_geom, mg_launch.hip.)
+inline mg::TileGeom field_geom(int nx, int ny, int ld) {
+  using S = mg::TileShape<double>;
+  mg::TileGeom g;
+  g.nx = nx; g.ny = ny; g.ld = ld;
+  g.nyv = std::min(ld, (ny + S::N - 1) / S::N * S::N);
+  g.i_org = 0;
+  g.tiles_j = (ny + S::TJ - 1) / S::TJ;
+  g.ntiles = (nx + mg::kTI - 1) / mg::kTI * g.tiles_j;
+  return g;
+}
 
 // dtype codes -> element types: calls f with a float (MG_F32) or double (anything else) value per code, so that the
 // generic lambda f names the types with decltype.  Every combination is instantiated: a site that accepts fewer rejects
@@ -257,6 +332,10 @@ int d_nl_eval(int kind, const double* u, const double* delta, double t, const do
 // hipMemset on device memory is asynchronous to the host and runs on the NULL stream, which a
 // hipStreamNonBlocking stream does not wait for: alloc_zero zeroes on the stream that will use the memory.
 int alloc_zero(std::string* err, void** p, size_t bytes, hipStream_t st = nullptr);
+// host array (nx, ny) of hdt <-> device field of ddt with pitch ld, on st; another dtype goes through `staging` (a device
+// field of the host dtype's pitch) and is cast on the device.  Both wait for st: the caller's array may go away
+int upload(std::string* err, void* dev, int ddt, int ld, const void* host, int hdt, int nx, int ny, void* staging,
+           hipStream_t st);
 int download(std::string* err, void* host, int hdt, const void* dev, int ddt, int ld, int nx, int ny, void* staging,
              hipStream_t st);
 int set_rhs_impl(mg_handle* h, const void* rhs, int hdt);
@@ -266,6 +345,12 @@ int set_u_impl(mg_handle* h, const void* u0, int hdt);
 int set_u_device_impl(mg_handle* h, const void* u_dev, int ld, int dtype);
 // after mg_set_rhs_device: the ring of that right-hand side (and of every later mg_update_rhs_device) is zero, so its sum is 0
 void rhs_ring_is_zero(mg_handle* h);
+// hand an engine another unit owns the fp64 device right-hand side f (pitch ld): mg_set_rhs_device the first time (then,
+// with ring_is_zero, rhs_ring_is_zero), mg_update_rhs_device afterwards; *has_rhs is the owner's flag.  Returns the
+// engine's code (its message is mg_last_error(eng))
+int engine_set_rhs(mg_handle* eng, bool* has_rhs, const double* f, int ld, bool ring_is_zero);
+// z = M r: num_cycles cycles from the zero iterate on the engine (the ring of r is zero: mg_update_rhs_device's contract)
+int engine_precondition(mg_handle* eng, bool* has_rhs, const double* r, double* z, int ld, int num_cycles);
 // mg_pcg.hip: the preconditioner engine an mg_pcg owns (its stream carries all of the solver's work), for the unit of the
 // library that owns an mg_pcg (mg_heat.hip) and queues its own kernels in between
 mg_handle* pcg_engine(mg_pcg* s);

@@ -159,19 +159,16 @@ bool line_shape_ok(int nx, int ny) { return nx >= 3 && ny >= 3 && nx - 2 <= kMax
 
 using namespace mgh;
 
-#define CHECK_LINE(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
-static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 extern "C" {
 
 int mg_line_plan_create(int dtype, int direction, int nx, int ny, int ld, double hx, double hy, double sigma, mg_line_plan** out) {
-  CHECK_LINE(out, "mg_line_plan_create: out is NULL");
+  CHECK_ARG(out, "mg_line_plan_create: out is NULL");
   *out = nullptr;
-  CHECK_LINE(valid_dtype(dtype) && (direction == MG_ZEBRA_X || direction == MG_ZEBRA_Y), "mg_line_plan_create: bad dtype / direction");
-  CHECK_LINE(nx >= 3 && ny >= 3 && ld >= ny && ((size_t)ld * esize(dtype)) % 16 == 0, "mg_line_plan_create: bad shape / pitch");
-  CHECK_LINE(hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy) && sigma >= 0.0 && std::isfinite(sigma),
+  CHECK_ARG(valid_dtype(dtype) && (direction == MG_ZEBRA_X || direction == MG_ZEBRA_Y), "mg_line_plan_create: bad dtype / direction");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld >= ny && ((size_t)ld * esize(dtype)) % 16 == 0, "mg_line_plan_create: bad shape / pitch");
+  CHECK_ARG(hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy) && sigma >= 0.0 && std::isfinite(sigma),
              "mg_line_plan_create: spacings must be positive, sigma finite and >= 0");
-  CHECK_LINE((direction == MG_ZEBRA_X ? nx : ny) - 2 <= kMaxLine, "mg_line_plan_create: lines of more than 16384 cells do not fit a workgroup's LDS");
+  CHECK_ARG((direction == MG_ZEBRA_X ? nx : ny) - 2 <= kMaxLine, "mg_line_plan_create: lines of more than 16384 cells do not fit a workgroup's LDS");
   int ndev = 0;
   const int rc = mg_device_count(&ndev);
   if (rc != MG_OK) return rc;
@@ -185,8 +182,8 @@ int mg_line_plan_destroy(mg_line_plan* p) {
 }
 
 int mg_dev_line_colour(mg_line_plan* p, int colour, double omega, void* u, const void* rhs, void* stream) {
-  CHECK_LINE(p && (colour == 0 || colour == 1) && std::isfinite(omega), "mg_dev_line_colour: bad argument");
-  CHECK_LINE(u && rhs && u != rhs && aligned16(u) && aligned16(rhs), "mg_dev_line_colour: bad pointer");
+  CHECK_ARG(p && (colour == 0 || colour == 1) && std::isfinite(omega), "mg_dev_line_colour: bad argument");
+  CHECK_ARG(u && rhs && u != rhs && aligned16(u) && aligned16(rhs), "mg_dev_line_colour: bad pointer");
   d_line_colour(p, colour, omega, u, rhs, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;
@@ -194,11 +191,11 @@ int mg_dev_line_colour(mg_line_plan* p, int colour, double omega, void* u, const
 
 int mg_op_zebra(int dtype, int smoother, int nx, int ny, double hx, double hy, double sigma, double omega, int nu,
                 const void* u, const void* rhs, void* out) {
-  CHECK_LINE(valid_dtype(dtype) && smoother >= MG_ZEBRA_X && smoother <= MG_ZEBRA_ALT && u && rhs && out && nu >= 0 && nx >= 3 && ny >= 3,
+  CHECK_ARG(valid_dtype(dtype) && smoother >= MG_ZEBRA_X && smoother <= MG_ZEBRA_ALT && u && rhs && out && nu >= 0 && nx >= 3 && ny >= 3,
              "mg_op_zebra: bad argument");
-  CHECK_LINE(hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy) && sigma >= 0.0 && std::isfinite(sigma) && std::isfinite(omega),
+  CHECK_ARG(hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy) && sigma >= 0.0 && std::isfinite(sigma) && std::isfinite(omega),
              "mg_op_zebra: spacings must be positive, sigma finite and >= 0");
-  CHECK_LINE((smoother == MG_ZEBRA_Y || nx - 2 <= kMaxLine) && (smoother == MG_ZEBRA_X || ny - 2 <= kMaxLine),
+  CHECK_ARG((smoother == MG_ZEBRA_Y || nx - 2 <= kMaxLine) && (smoother == MG_ZEBRA_X || ny - 2 <= kMaxLine),
              "mg_op_zebra: lines of more than 16384 cells do not fit a workgroup's LDS");
   const int ld = pitch_elems(dtype, ny);
   const size_t pitch = (size_t)ld * esize(dtype), wbytes = (size_t)ny * esize(dtype);
@@ -231,7 +228,7 @@ int mg_op_zebra(int dtype, int smoother, int nx, int ny, double hx, double hy, d
 }
 
 int mg_line_time_sweep(mg_line_plan* p, int reps, double* avg_ms) {
-  CHECK_LINE(p && avg_ms && reps >= 1, "mg_line_time_sweep: bad argument");
+  CHECK_ARG(p && avg_ms && reps >= 1, "mg_line_time_sweep: bad argument");
   const size_t elems = (size_t)p->nx * p->ld, bytes = elems * esize(p->dtype);
   void *du = nullptr, *df = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;

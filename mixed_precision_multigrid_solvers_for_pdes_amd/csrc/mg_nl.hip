@@ -22,13 +22,7 @@ namespace mgh {
 int d_nl_eval(int kind, const double* u, const double* delta, double t, const double* a, const double* w, const double* f,
               double* u_out, double* F, double* c, double* partials, int* second, int nx, int ny, int ld, double hx, double hy,
               double coeff, double sigma, double kappa, hipStream_t st) {
-  using S = mg::TileShape<double>;
-  mg::TileGeom g;
-  g.nx = nx; g.ny = ny; g.ld = ld;
-  g.nyv = std::min(ld, (ny + S::N - 1) / S::N * S::N);
-  g.i_org = 0;
-  g.tiles_j = (ny + S::TJ - 1) / S::TJ;
-  g.ntiles = (nx + mg::kTI - 1) / mg::kTI * g.tiles_j;
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const Coef cf = coefs(hx, hy, sigma);
   mg::NlArgs n;
   n.ihx2 = cf.ihx2; n.ihy2 = cf.ihy2; n.diag = cf.diag; n.coeff = coeff; n.sigma = sigma;
@@ -76,20 +70,6 @@ mg_handle* nl_engine(mg_nl* s) { return pcg_engine(s->pcg); }
 
 namespace {
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-bool ld_ok(int ny, int ld) { return ld >= ny && ld % 2 == 0; }
-bool kind_ok(int kind) { return kind >= MG_NL_LINEAR && kind <= MG_NL_EXP; }
-bool operator_ok(double hx, double hy, double coeff, double sigma) {
-  return hx > 0.0 && hy > 0.0 && std::isfinite(hx) && std::isfinite(hy) && std::isfinite(coeff) && sigma >= 0.0 && std::isfinite(sigma);
-}
-bool kappa_ok(double kappa) { return kappa >= 0.0 && std::isfinite(kappa); }
-// every entry of the host weight field finite and >= 0
-template <typename T> bool weight_ok(const T* w, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!(w[k] >= T(0)) || !std::isfinite((double)w[k])) return false;
-  return true;
-}
-
 void options_default(mg_nl_options* o) {
   o->forcing = MG_NL_FORCING_EISENSTAT_WALKER;
   o->max_backtracks = 10;
@@ -101,15 +81,6 @@ void options_default(mg_nl_options* o) {
   o->eta_min = 1e-10;
 }
 
-int nfail(mg_nl* s, int code, const std::string& msg) { return fail(s ? &s->err : nullptr, code, msg); }
-int pcg_rc(mg_nl* s, int rc) {
-  if (rc != MG_OK) nfail(s, rc, std::string("inner solver: ") + mg_pcg_last_error(s->pcg));
-  return rc;
-}
-#define PCG(call) do { const int rc_ = pcg_rc(s, (call)); if (rc_ != MG_OK) return rc_; } while (0)
-
-size_t field_bytes(const mg_nl* s) { return (size_t)s->nx * s->ld * sizeof(double); }
-
 void release(mg_nl* s) {
   if (s->pcg) { (void)mg_pcg_destroy(s->pcg); s->pcg = nullptr; }
   for (double** p : {&s->u[0], &s->u[1], &s->F[0], &s->F[1], &s->c[0], &s->c[1], &s->delta, &s->f, &s->a, &s->w, &s->staging,
@@ -119,17 +90,8 @@ void release(mg_nl* s) {
 }
 
 // host array (nx, ny) of hdt -> fp64 device field with the solver's pitch, on the engine's stream
-int upload(mg_nl* s, double* dev, const void* host, int hdt) {
-  const size_t es = esize(hdt);
-  if (hdt == MG_F64) {
-    HIPC(&s->err, hipMemcpy2DAsync(dev, (size_t)s->ld * 8, host, (size_t)s->ny * 8, (size_t)s->ny * 8, s->nx, hipMemcpyHostToDevice, s->st));
-  } else {
-    const int lds = pitch_elems(hdt, s->ny);
-    HIPC(&s->err, hipMemcpy2DAsync(s->staging, (size_t)lds * es, host, (size_t)s->ny * es, (size_t)s->ny * es, s->nx, hipMemcpyHostToDevice, s->st));
-    d_convert(hdt, MG_F64, s->staging, dev, s->nx, s->ny, lds, s->ld, s->st);
-  }
-  HIPC(&s->err, hipStreamSynchronize(s->st));      // the caller's array may go away
-  return MG_OK;
+int put(mg_nl* s, double* dev, const void* host, int hdt) {
+  return upload(&s->err, dev, MG_F64, s->ld, host, hdt, s->nx, s->ny, s->staging, s->st);
 }
 
 // One Newton trial: v = u[cur] + t delta (with_delta) into u[into], F(v) and c(v) into F[into] and c[into]; the host gets the
@@ -177,12 +139,12 @@ int solve_resident(mg_nl* s, double tol, int max_newton, double* norm_hist, int*
       }
     }
     const double inner_tol = std::max(eta * norm, 0.1 * tol);
-    PCG(mg_pcg_set_reaction_device(s->pcg, s->c[s->cur], s->ld, cbar));
+    OWNED(mg_pcg_set_reaction_device(s->pcg, s->c[s->cur], s->ld, cbar), "inner solver: ", mg_pcg_last_error(s->pcg));
     HIPC(&s->err, hipMemsetAsync(s->delta, 0, field_bytes(s), s->st));
     int n_in = 0, conv_in = 0;
     mg_pcg_stats ps;
-    PCG(mg_pcg_solve_device(s->pcg, s->F[s->cur], s->ld, s->delta, s->ld, MG_F64, inner_tol, o.max_inner, inner_norms.data(),
-                            o.max_inner, &n_in, &conv_in, &ps));
+    OWNED(mg_pcg_solve_device(s->pcg, s->F[s->cur], s->ld, s->delta, s->ld, MG_F64, inner_tol, o.max_inner, inner_norms.data(),
+                            o.max_inner, &n_in, &conv_in, &ps), "inner solver: ", mg_pcg_last_error(s->pcg));
     inner_total += n_in;
     if (ps.status == 2 && n_in == 0) { status = 2; break; }
     // backtracking: the trial goes to the spare buffers, a rejected one is overwritten by the next
@@ -208,7 +170,7 @@ int solve_resident(mg_nl* s, double tol, int max_newton, double* norm_hist, int*
     ++k;
   }
   // the inner solver goes back to the plain loop: the field it was lent is rewritten by the next solve
-  PCG(mg_pcg_set_reaction_device(s->pcg, nullptr, 0, 0.0));
+  OWNED(mg_pcg_set_reaction_device(s->pcg, nullptr, 0, 0.0), "inner solver: ", mg_pcg_last_error(s->pcg));
   *n_newton = k;
   *converged = status == 0 ? 1 : 0;
   if (stats) {
@@ -226,15 +188,13 @@ int solve_resident(mg_nl* s, double tol, int max_newton, double* norm_hist, int*
 int solve_args_ok(mg_nl* s, const char* who, const void* f, const void* out, int dtype, double tol, int max_newton, double* hist,
                   int hist_cap, int* n_newton, int* converged) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, std::string(who) + ": NULL solver");
-  if (!f || !out || !hist || !n_newton || !converged) return nfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": NULL argument");
+  if (!f || !out || !hist || !n_newton || !converged) return sfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": NULL argument");
   if (!valid_dtype(dtype) || hist_cap < 1 || max_newton < 1 || !(tol == tol))
-    return nfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": bad dtype / hist_cap < 1 / max_newton < 1 / tol is NaN");
+    return sfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": bad dtype / hist_cap < 1 / max_newton < 1 / tol is NaN");
   return MG_OK;
 }
 
 }  // namespace
-
-#define CHECK_NL(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
 
 extern "C" {
 
@@ -242,18 +202,18 @@ int mg_dev_nl_eval(int kind, int nx, int ny, int ld, double hx, double hy, doubl
                    const double* a_or_null, const double* w_or_null, const double* u, const double* delta_or_null, double t,
                    const double* f, double* u_out_or_null, double* F_or_null, double* c_or_null, void* scratch, double* sums_dev,
                    void* stream) {
-  CHECK_NL(kind_ok(kind), "mg_dev_nl_eval: unknown nonlinearity");
-  CHECK_NL(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && operator_ok(hx, hy, coeff, sigma), "mg_dev_nl_eval: bad shape / pitch / spacing / shift");
-  CHECK_NL(kappa_ok(kappa), "mg_dev_nl_eval: kappa must be finite and >= 0 (monotone nonlinearities only)");
-  CHECK_NL(!delta_or_null || std::isfinite(t), "mg_dev_nl_eval: the step length must be finite");
-  CHECK_NL(u && f && scratch && sums_dev, "mg_dev_nl_eval: NULL pointer");
+  CHECK_ARG(kind_ok(kind, MG_NL_LINEAR, MG_NL_EXP), "mg_dev_nl_eval: unknown nonlinearity");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && operator_ok(hx, hy, coeff, sigma), "mg_dev_nl_eval: bad shape / pitch / spacing / shift");
+  CHECK_ARG(kappa_ok(kappa), "mg_dev_nl_eval: kappa must be finite and >= 0 (monotone nonlinearities only)");
+  CHECK_ARG(!delta_or_null || std::isfinite(t), "mg_dev_nl_eval: the step length must be finite");
+  CHECK_ARG(u && f && scratch && sums_dev, "mg_dev_nl_eval: NULL pointer");
   double* uo = delta_or_null ? u_out_or_null : nullptr;
   for (const double* out : {(const double*)uo, (const double*)F_or_null, (const double*)c_or_null})
-    CHECK_NL(!out || (out != u && out != f && out != delta_or_null && out != a_or_null && out != w_or_null),
+    CHECK_ARG(!out || (out != u && out != f && out != delta_or_null && out != a_or_null && out != w_or_null),
              "mg_dev_nl_eval: outputs are arrays of their own");
-  CHECK_NL((!uo || (uo != F_or_null && uo != c_or_null)) && (!F_or_null || F_or_null != c_or_null),
+  CHECK_ARG((!uo || (uo != F_or_null && uo != c_or_null)) && (!F_or_null || F_or_null != c_or_null),
            "mg_dev_nl_eval: outputs are arrays of their own");
-  CHECK_NL(aligned16(u) && aligned16(f) && aligned16(delta_or_null) && aligned16(a_or_null) && aligned16(w_or_null) && aligned16(uo) &&
+  CHECK_ARG(aligned16(u) && aligned16(f) && aligned16(delta_or_null) && aligned16(a_or_null) && aligned16(w_or_null) && aligned16(uo) &&
            aligned16(F_or_null) && aligned16(c_or_null) && aligned16(scratch), "mg_dev_nl_eval: unaligned pointer");
   int second = 0;
   const int n = d_nl_eval(kind, u, delta_or_null, t, a_or_null, w_or_null, f, uo, F_or_null, c_or_null, (double*)scratch, &second, nx,
@@ -267,11 +227,11 @@ int mg_dev_nl_eval(int kind, int nx, int ny, int ld, double hx, double hy, doubl
 int mg_op_nl_eval(int kind, int nx, int ny, double hx, double hy, double coeff, double sigma, double kappa, const double* a_or_null,
                   const double* w_or_null, const double* u, const double* delta_or_null, double t, const double* f,
                   double* u_out_or_null, double* F_or_null, double* c_or_null, double* sums) {
-  CHECK_NL(kind_ok(kind), "mg_op_nl_eval: unknown nonlinearity");
-  CHECK_NL(nx >= 3 && ny >= 3 && operator_ok(hx, hy, coeff, sigma) && u && f && sums, "mg_op_nl_eval: bad argument");
-  CHECK_NL(kappa_ok(kappa), "mg_op_nl_eval: kappa must be finite and >= 0 (monotone nonlinearities only)");
-  CHECK_NL(!w_or_null || weight_ok(w_or_null, (size_t)nx * ny), "mg_op_nl_eval: the weight field must be finite and >= 0");
-  CHECK_NL(!delta_or_null || std::isfinite(t), "mg_op_nl_eval: the step length must be finite");
+  CHECK_ARG(kind_ok(kind, MG_NL_LINEAR, MG_NL_EXP), "mg_op_nl_eval: unknown nonlinearity");
+  CHECK_ARG(nx >= 3 && ny >= 3 && operator_ok(hx, hy, coeff, sigma) && u && f && sums, "mg_op_nl_eval: bad argument");
+  CHECK_ARG(kappa_ok(kappa), "mg_op_nl_eval: kappa must be finite and >= 0 (monotone nonlinearities only)");
+  CHECK_ARG(!w_or_null || weight_ok(w_or_null, (size_t)nx * ny), "mg_op_nl_eval: the weight field must be finite and >= 0");
+  CHECK_ARG(!delta_or_null || std::isfinite(t), "mg_op_nl_eval: the step length must be finite");
   const int ld = pitch_elems(MG_F64, ny);
   const size_t pitch = (size_t)ld * 8, wbytes = (size_t)ny * 8;
   const double* in[5] = {u, f, delta_or_null, a_or_null, w_or_null};
@@ -335,7 +295,7 @@ int mg_nl_create(const mg_config* cfg, int num_cycles, int flexible, mg_nl** out
   s->ld = pitch_elems(MG_F64, cfg->ny);
   s->hx = eng->lv[0].hx; s->hy = eng->lv[0].hy;
   options_default(&s->opt);
-  auto bail = [&](int code) { release(s); const std::string m = s->err; delete s; last_error() = m; return code; };
+  auto bail = [&](int code) { return create_fail(s, release, code); };
   for (double** p : {&s->u[0], &s->u[1], &s->F[0], &s->F[1], &s->c[0], &s->c[1], &s->delta, &s->f, &s->staging})
     if ((rc = alloc_zero(&s->err, (void**)p, field_bytes(s), s->st)) != MG_OK) return bail(rc);
   if ((rc = alloc_zero(&s->err, (void**)&s->partials, sizeof(double) * 2 * max_partials(s->nx, s->ny), s->st)) != MG_OK) return bail(rc);
@@ -347,47 +307,42 @@ int mg_nl_create(const mg_config* cfg, int num_cycles, int flexible, mg_nl** out
 }
 
 int mg_nl_destroy(mg_nl* s) {
-  if (!s) return MG_OK;
-  (void)hipSetDevice(s->cfg.device);
-  if (s->st) (void)hipStreamSynchronize(s->st);
-  release(s);
-  delete s;
-  return MG_OK;
+  return destroy_owned(s, s ? s->st : nullptr, release);
 }
 
 const char* mg_nl_last_error(const mg_nl* s) { return s ? s->err.c_str() : last_error().c_str(); }
 
 int mg_nl_set_coefficient(mg_nl* s, const void* a_host_or_null, int host_dtype) {
-  if (!s || !valid_dtype(host_dtype)) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_coefficient: bad argument");
+  if (!s || !valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_coefficient: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  PCG(mg_pcg_set_coefficient(s->pcg, a_host_or_null, host_dtype));
+  OWNED(mg_pcg_set_coefficient(s->pcg, a_host_or_null, host_dtype), "inner solver: ", mg_pcg_last_error(s->pcg));
   if (!a_host_or_null) { s->varcoef = false; return MG_OK; }
   if (!s->a) { const int rc = alloc_zero(&s->err, (void**)&s->a, field_bytes(s), s->st); if (rc != MG_OK) return rc; }
-  const int rc = upload(s, s->a, a_host_or_null, host_dtype);
+  const int rc = put(s, s->a, a_host_or_null, host_dtype);
   if (rc != MG_OK) return rc;
   s->varcoef = true;
   return MG_OK;
 }
 
 int mg_nl_set_shift(mg_nl* s, double sigma) {
-  if (!s || !(sigma >= 0.0) || !std::isfinite(sigma)) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_shift: sigma must be finite and >= 0");
-  PCG(mg_pcg_set_shift(s->pcg, sigma));
+  if (!s || !(sigma >= 0.0) || !std::isfinite(sigma)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_shift: sigma must be finite and >= 0");
+  OWNED(mg_pcg_set_shift(s->pcg, sigma), "inner solver: ", mg_pcg_last_error(s->pcg));
   s->sigma = sigma;
   return MG_OK;
 }
 
 int mg_nl_set_nonlinearity(mg_nl* s, int kind, double kappa, const void* w_host_or_null, int host_dtype) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: NULL solver");
-  if (!kind_ok(kind)) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: unknown nonlinearity (mg_nl_kind)");
-  if (!kappa_ok(kappa)) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: kappa must be finite and >= 0 (monotone nonlinearities only)");
-  if (!valid_dtype(host_dtype)) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: bad dtype");
+  if (!kind_ok(kind, MG_NL_LINEAR, MG_NL_EXP)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: unknown nonlinearity (mg_nl_kind)");
+  if (!kappa_ok(kappa)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: kappa must be finite and >= 0 (monotone nonlinearities only)");
+  if (!valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: bad dtype");
   if (w_host_or_null) {
     const size_t n = (size_t)s->nx * s->ny;
     const bool ok = host_dtype == MG_F32 ? weight_ok((const float*)w_host_or_null, n) : weight_ok((const double*)w_host_or_null, n);
-    if (!ok) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: the weight field must be finite and >= 0 (monotone nonlinearities only)");
+    if (!ok) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_nonlinearity: the weight field must be finite and >= 0 (monotone nonlinearities only)");
     HIPC(&s->err, hipSetDevice(s->cfg.device));
     if (!s->w) { const int rc = alloc_zero(&s->err, (void**)&s->w, field_bytes(s), s->st); if (rc != MG_OK) return rc; }
-    const int rc = upload(s, s->w, w_host_or_null, host_dtype);
+    const int rc = put(s, s->w, w_host_or_null, host_dtype);
     if (rc != MG_OK) return rc;
   }
   s->has_w = w_host_or_null != nullptr;
@@ -397,11 +352,11 @@ int mg_nl_set_nonlinearity(mg_nl* s, int kind, double kappa, const void* w_host_
 }
 
 int mg_nl_set_options(mg_nl* s, const mg_nl_options* o) {
-  if (!s || !o) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_options: NULL argument");
+  if (!s || !o) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_options: NULL argument");
   const bool ok = (o->forcing == MG_NL_FORCING_EISENSTAT_WALKER || o->forcing == MG_NL_FORCING_FIXED) && o->max_backtracks >= 0 &&
                   o->max_inner >= 1 && o->eta > 0.0 && o->eta < 1.0 && o->gamma > 0.0 && o->gamma <= 1.0 && o->eta_min > 0.0 &&
                   o->eta_min <= o->eta_max && o->eta_max < 1.0;
-  if (!ok) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_options: forcing / max_backtracks >= 0 / max_inner >= 1 / 0 < eta < 1 / 0 < gamma <= 1 / 0 < eta_min <= eta_max < 1");
+  if (!ok) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_set_options: forcing / max_backtracks >= 0 / max_inner >= 1 / 0 < eta < 1 / 0 < gamma <= 1 / 0 < eta_min <= eta_max < 1");
   s->opt = *o;
   return MG_OK;
 }
@@ -411,7 +366,7 @@ int mg_nl_solve_device(mg_nl* s, const void* f_dev, int ld_f, void* u_dev, int l
                        int* converged, mg_nl_stats* stats) {
   int rc = solve_args_ok(s, "mg_nl_solve_device", f_dev, u_dev, dtype, tol, max_newton, norm_hist, hist_cap, n_newton, converged);
   if (rc != MG_OK) return rc;
-  if (ld_f < s->ny || ld_u < s->ny) return nfail(s, MG_ERR_INVALID_VALUE, "mg_nl_solve_device: pitch smaller than ny");
+  if (ld_f < s->ny || ld_u < s->ny) return sfail(s, MG_ERR_INVALID_VALUE, "mg_nl_solve_device: pitch smaller than ny");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   d_convert(dtype, MG_F64, f_dev, s->f, s->nx, s->ny, ld_f, s->ld, s->st);
   d_convert(dtype, MG_F64, u_dev, s->u[s->cur], s->nx, s->ny, ld_u, s->ld, s->st);
@@ -431,8 +386,8 @@ int mg_nl_solve(mg_nl* s, const void* f, const void* u0_or_null, void* u_out, in
   int rc = solve_args_ok(s, "mg_nl_solve", f, u_out, host_dtype, tol, max_newton, norm_hist, hist_cap, n_newton, converged);
   if (rc != MG_OK) return rc;
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  if ((rc = upload(s, s->f, f, host_dtype)) != MG_OK) return rc;
-  if (u0_or_null) { if ((rc = upload(s, s->u[s->cur], u0_or_null, host_dtype)) != MG_OK) return rc; }
+  if ((rc = put(s, s->f, f, host_dtype)) != MG_OK) return rc;
+  if (u0_or_null) { if ((rc = put(s, s->u[s->cur], u0_or_null, host_dtype)) != MG_OK) return rc; }
   else HIPC(&s->err, hipMemsetAsync(s->u[s->cur], 0, field_bytes(s), s->st));
   if ((rc = solve_resident(s, tol, max_newton, norm_hist, inner_hist, step_hist, eta_hist, hist_cap, n_newton, converged, stats)) != MG_OK) {
     (void)hipStreamSynchronize(s->st);

@@ -65,17 +65,6 @@ struct mg_pcg {
 
 namespace {
 
-mg::TileGeom pcg_geom(int nx, int ny, int ld) {
-  using S = mg::TileShape<double>;
-  mg::TileGeom g;
-  g.nx = nx; g.ny = ny; g.ld = ld;
-  g.nyv = std::min(ld, (ny + S::N - 1) / S::N * S::N);
-  g.i_org = 0;
-  g.tiles_j = (ny + S::TJ - 1) / S::TJ;
-  g.ntiles = (nx + mg::kTI - 1) / mg::kTI * g.tiles_j;
-  return g;
-}
-
 int stream_blocks(int nx, int nyv) {
   const long long vecs = (long long)(nx - 2) * (nyv / 2);
   return (int)std::max<long long>(1, std::min<long long>((vecs + mg::kBlock - 1) / mg::kBlock, 1024));
@@ -85,7 +74,7 @@ int stream_blocks(int nx, int nyv) {
 int launch_direction(const double* z, const double* p_in, double* p_out, double* q, const double* a, const double* creact,
                      const double* beta, double* partials, int nx, int ny, int ld, double hx, double hy, double coeff, double sigma,
                      hipStream_t st) {
-  const mg::TileGeom g = pcg_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const Coef c = coefs(hx, hy, sigma);
   auto k = creact ? (a ? mg::pcg_direction_kernel<true, true> : mg::pcg_direction_kernel<false, true>)
                   : (a ? mg::pcg_direction_kernel<true, false> : mg::pcg_direction_kernel<false, false>);
@@ -96,7 +85,7 @@ int launch_direction(const double* z, const double* p_in, double* p_out, double*
 
 int launch_update(const double* alpha, const double* p, const double* q, double* x, double* r, double* partials, int nx, int ny,
                   int ld, hipStream_t st) {
-  const mg::TileGeom g = pcg_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const int nb = stream_blocks(nx, g.nyv);
   hipLaunchKernelGGL(mg::pcg_update_kernel, dim3(nb), dim3(mg::kBlock), 0, st, alpha, p, q, x, r, partials, nx, ny, g.nyv, ld);
   return nb;
@@ -104,7 +93,7 @@ int launch_update(const double* alpha, const double* p, const double* q, double*
 
 int launch_dots(const double* r, const double* z, const double* q, double* partials, int second, int nx, int ny, int ld,
                 hipStream_t st) {
-  const mg::TileGeom g = pcg_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const int nb = stream_blocks(nx, g.nyv);
   auto k = q ? mg::pcg_dots_kernel<true> : mg::pcg_dots_kernel<false>;
   hipLaunchKernelGGL(k, dim3(nb), dim3(mg::kBlock), 0, st, r, z, q, partials, second, nx, ny, g.nyv, ld);
@@ -116,15 +105,6 @@ void launch_scalars(int op, const double* pa, int na, const double* pb, int nb, 
   hipLaunchKernelGGL(mg::pcg_scalars_kernel, dim3(1), dim3(mg::kReduceBlock), 0, st, op, pa, na, pb, nb, sc, mbox, seq);
 }
 
-int pfail(mg_pcg* s, int code, const std::string& msg) { return fail(s ? &s->err : nullptr, code, msg); }
-
-// the engine's message joins the solver's
-int eng_rc(mg_pcg* s, int rc) {
-  if (rc != MG_OK) pfail(s, rc, std::string("preconditioner: ") + mg_last_error(s->eng));
-  return rc;
-}
-#define ENG(call) do { const int rc_ = eng_rc(s, (call)); if (rc_ != MG_OK) return rc_; } while (0)
-
 void release(mg_pcg* s) {
   if (s->eng) { (void)mg_destroy(s->eng); s->eng = nullptr; }
   for (double** p : {&s->x, &s->r, &s->z, &s->q, &s->f, &s->a, &s->g, &s->staging, &s->p[0], &s->p[1], &s->partials, &s->sc})
@@ -135,31 +115,9 @@ void release(mg_pcg* s) {
   s->nev = 0;
 }
 
-size_t field_bytes(const mg_pcg* s) { return (size_t)s->nx * s->ld * sizeof(double); }
-
 // host array (nx, ny) of hdt -> fp64 device field with the solver's pitch, on the engine's stream
-int upload(mg_pcg* s, double* dev, const void* host, int hdt) {
-  hipStream_t st = s->eng->stream;
-  const size_t es = esize(hdt);
-  if (hdt == MG_F64) {
-    HIPC(&s->err, hipMemcpy2DAsync(dev, (size_t)s->ld * 8, host, (size_t)s->ny * 8, (size_t)s->ny * 8, s->nx, hipMemcpyHostToDevice, st));
-  } else {
-    const int lds = pitch_elems(hdt, s->ny);
-    HIPC(&s->err, hipMemcpy2DAsync(s->staging, (size_t)lds * es, host, (size_t)s->ny * es, (size_t)s->ny * es, s->nx, hipMemcpyHostToDevice, st));
-    d_convert(hdt, MG_F64, s->staging, dev, s->nx, s->ny, lds, s->ld, st);
-  }
-  HIPC(&s->err, hipStreamSynchronize(st));      // the caller's array may go away
-  return MG_OK;
-}
-
-// z = M r: num_cycles cycles from the zero iterate on the engine (the ring of r is zero: mg_update_rhs_device's contract)
-int precondition(mg_pcg* s) {
-  if (!s->eng_has_rhs) { ENG(mg_set_rhs_device(s->eng, s->r, s->ld, MG_F64)); s->eng_has_rhs = true; }
-  else ENG(mg_update_rhs_device(s->eng, s->r, s->ld, MG_F64));
-  ENG(mg_zero_solution_device(s->eng));
-  ENG(mg_cycle(s->eng, s->num_cycles));
-  ENG(mg_get_solution_device(s->eng, s->z, s->ld, MG_F64));
-  return MG_OK;
+int put(mg_pcg* s, double* dev, const void* host, int hdt) {
+  return upload(&s->err, dev, MG_F64, s->ld, host, hdt, s->nx, s->ny, s->staging, s->eng->stream);
 }
 
 // everything of iteration k that x and r do not depend on: z, the dots, beta, the new direction, q and alpha
@@ -167,8 +125,7 @@ int front(mg_pcg* s, int k) {
   hipStream_t st = s->eng->stream;
   const bool timed = k < kTimedIters && s->nev == 2 * kTimedIters;
   if (timed) HIPC(&s->err, hipEventRecord(s->ev[2 * k], st));
-  const int rc = precondition(s);
-  if (rc != MG_OK) return rc;
+  OWNED(engine_precondition(s->eng, &s->eng_has_rhs, s->r, s->z, s->ld, s->num_cycles), "preconditioner: ", mg_last_error(s->eng));      // z = M r
   if (timed) HIPC(&s->err, hipEventRecord(s->ev[2 * k + 1], st));
   const bool flex = s->flexible && k > 0;
   const int nd = launch_dots(s->r, s->z, flex ? s->q : nullptr, s->partials, s->np, s->nx, s->ny, s->ld, st);
@@ -321,15 +278,12 @@ int solve_resident(mg_pcg* s, double tol, int max_iter, double* hist, int hist_c
   return MG_OK;
 }
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-bool ld_ok(int ny, int ld) { return ld >= ny && ld % 2 == 0; }
-
 int solve_args_ok(mg_pcg* s, const char* who, const void* rhs, const void* out, int dtype, double tol, int max_iter, double* hist,
                   int hist_cap, int* n_iter, int* converged) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, std::string(who) + ": NULL solver");
-  if (!rhs || !out || !hist || !n_iter || !converged) return pfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": NULL argument");
+  if (!rhs || !out || !hist || !n_iter || !converged) return sfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": NULL argument");
   if (!valid_dtype(dtype) || hist_cap < 1 || max_iter < 1 || !(tol == tol))
-    return pfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": bad dtype / hist_cap < 1 / max_iter < 1 / tol is NaN");
+    return sfail(s, MG_ERR_INVALID_VALUE, std::string(who) + ": bad dtype / hist_cap < 1 / max_iter < 1 / tol is NaN");
   return MG_OK;
 }
 
@@ -338,8 +292,6 @@ int solve_args_ok(mg_pcg* s, const char* who, const void* rhs, const void* out, 
 namespace mgh {
 mg_handle* pcg_engine(mg_pcg* s) { return s ? s->eng : nullptr; }
 }  // namespace mgh
-
-#define CHECK_DEV(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
 
 extern "C" {
 
@@ -359,11 +311,11 @@ int mg_pcg_create(const mg_config* cfg, int num_cycles, int flexible, mg_pcg** o
   s->eng = eng;
   s->nx = cfg->nx; s->ny = cfg->ny;
   s->ld = pitch_elems(MG_F64, cfg->ny);
-  s->nyv = pcg_geom(s->nx, s->ny, s->ld).nyv;
+  s->nyv = field_geom(s->nx, s->ny, s->ld).nyv;
   s->hx = eng->lv[0].hx; s->hy = eng->lv[0].hy;
   s->num_cycles = num_cycles;
   s->flexible = flexible < 0 ? (cfg->smoother != MG_JACOBI || cfg->pre != cfg->post) : (flexible != 0);
-  auto bail = [&](int code) { release(s); const std::string m = s->err; delete s; last_error() = m; return code; };
+  auto bail = [&](int code) { return create_fail(s, release, code); };
   hipStream_t st = eng->stream;
   for (double** p : {&s->x, &s->r, &s->z, &s->q, &s->f, &s->staging, &s->p[0], &s->p[1]})
     if ((rc = alloc_zero(&s->err, (void**)p, field_bytes(s), st)) != MG_OK) return bail(rc);
@@ -385,12 +337,7 @@ int mg_pcg_create(const mg_config* cfg, int num_cycles, int flexible, mg_pcg** o
 }
 
 int mg_pcg_destroy(mg_pcg* s) {
-  if (!s) return MG_OK;
-  (void)hipSetDevice(s->cfg.device);
-  if (s->eng && s->eng->stream) (void)hipStreamSynchronize(s->eng->stream);
-  release(s);
-  delete s;
-  return MG_OK;
+  return destroy_owned(s, s && s->eng ? s->eng->stream : nullptr, release);
 }
 
 const char* mg_pcg_last_error(const mg_pcg* s) { return s ? s->err.c_str() : last_error().c_str(); }
@@ -402,14 +349,14 @@ int mg_pcg_set_lookahead(mg_pcg* s, int on) {
 }
 
 int mg_pcg_set_coefficient(mg_pcg* s, const void* a_host_or_null, int host_dtype) {
-  if (!s || !valid_dtype(host_dtype)) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_coefficient: bad argument");
+  if (!s || !valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_coefficient: bad argument");
   if (a_host_or_null && s->order == 4)
-    return pfail(s, MG_ERR_STATE, "mg_pcg_set_coefficient: the fourth-order scheme needs constant coefficients (mg_pcg_set_order(2) first)");
+    return sfail(s, MG_ERR_STATE, "mg_pcg_set_coefficient: the fourth-order scheme needs constant coefficients (mg_pcg_set_order(2) first)");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  ENG(mg_set_coefficient(s->eng, a_host_or_null, host_dtype));
+  OWNED(mg_set_coefficient(s->eng, a_host_or_null, host_dtype), "preconditioner: ", mg_last_error(s->eng));
   if (!a_host_or_null) { s->varcoef = false; return MG_OK; }
   if (!s->a) { const int rc = alloc_zero(&s->err, (void**)&s->a, field_bytes(s), s->eng->stream); if (rc != MG_OK) return rc; }
-  const int rc = upload(s, s->a, a_host_or_null, host_dtype);
+  const int rc = put(s, s->a, a_host_or_null, host_dtype);
   if (rc != MG_OK) return rc;
   s->varcoef = true;
   return MG_OK;
@@ -417,11 +364,11 @@ int mg_pcg_set_coefficient(mg_pcg* s, const void* a_host_or_null, int host_dtype
 
 int mg_pcg_set_order(mg_pcg* s, int order) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_pcg_set_order: NULL solver");
-  if (order != 2 && order != 4) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_order: order must be 2 or 4");
+  if (order != 2 && order != 4) return sfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_order: order must be 2 or 4");
   if (order == 4 && s->varcoef)
-    return pfail(s, MG_ERR_STATE, "mg_pcg_set_order: the fourth-order scheme needs constant coefficients (mg_pcg_set_coefficient(NULL) first)");
+    return sfail(s, MG_ERR_STATE, "mg_pcg_set_order: the fourth-order scheme needs constant coefficients (mg_pcg_set_coefficient(NULL) first)");
   if (order == 4 && s->creact)
-    return pfail(s, MG_ERR_STATE, "mg_pcg_set_order: the fourth-order scheme takes no reaction field (mg_pcg_set_reaction_device(NULL) first)");
+    return sfail(s, MG_ERR_STATE, "mg_pcg_set_order: the fourth-order scheme takes no reaction field (mg_pcg_set_reaction_device(NULL) first)");
   if (order == 4 && !s->g) {
     HIPC(&s->err, hipSetDevice(s->cfg.device));
     const int rc = alloc_zero(&s->err, (void**)&s->g, field_bytes(s), s->eng->stream);
@@ -432,8 +379,8 @@ int mg_pcg_set_order(mg_pcg* s, int order) {
 }
 
 int mg_pcg_set_shift(mg_pcg* s, double sigma) {
-  if (!s || !(sigma >= 0.0) || !std::isfinite(sigma)) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_shift: sigma must be finite and >= 0");
-  ENG(mg_set_shift(s->eng, s->creact ? sigma + s->c_ref : sigma));
+  if (!s || !(sigma >= 0.0) || !std::isfinite(sigma)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_shift: sigma must be finite and >= 0");
+  OWNED(mg_set_shift(s->eng, s->creact ? sigma + s->c_ref : sigma), "preconditioner: ", mg_last_error(s->eng));
   s->sigma = sigma;
   return MG_OK;
 }
@@ -441,17 +388,17 @@ int mg_pcg_set_shift(mg_pcg* s, double sigma) {
 int mg_pcg_set_reaction_device(mg_pcg* s, const double* c_dev_or_null, int ld, double c_ref) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: NULL solver");
   if (!c_dev_or_null) {
-    if (s->creact) ENG(mg_set_shift(s->eng, s->sigma));
+    if (s->creact) OWNED(mg_set_shift(s->eng, s->sigma), "preconditioner: ", mg_last_error(s->eng));
     s->creact = nullptr;
     s->c_ref = 0.0;
     return MG_OK;
   }
   if (s->order == 4)
-    return pfail(s, MG_ERR_STATE, "mg_pcg_set_reaction_device: the fourth-order scheme takes no reaction field (mg_pcg_set_order(2) first)");
-  if (!(c_ref >= 0.0) || !std::isfinite(c_ref)) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: c_ref must be finite and >= 0");
+    return sfail(s, MG_ERR_STATE, "mg_pcg_set_reaction_device: the fourth-order scheme takes no reaction field (mg_pcg_set_order(2) first)");
+  if (!(c_ref >= 0.0) || !std::isfinite(c_ref)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: c_ref must be finite and >= 0");
   if (ld != s->ld || !aligned16(c_dev_or_null))
-    return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: the field has the solver's pitch (mg_pitch_elems) and 16-byte alignment");
-  ENG(mg_set_shift(s->eng, s->sigma + c_ref));
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_set_reaction_device: the field has the solver's pitch (mg_pitch_elems) and 16-byte alignment");
+  OWNED(mg_set_shift(s->eng, s->sigma + c_ref), "preconditioner: ", mg_last_error(s->eng));
   s->creact = c_dev_or_null;
   s->c_ref = c_ref;
   return MG_OK;
@@ -461,7 +408,7 @@ int mg_pcg_solve_device(mg_pcg* s, const void* rhs_dev, int ld_rhs, void* x_dev,
                         double* hist, int hist_cap, int* n_iter, int* converged, mg_pcg_stats* stats) {
   int rc = solve_args_ok(s, "mg_pcg_solve_device", rhs_dev, x_dev, dtype, tol, max_iter, hist, hist_cap, n_iter, converged);
   if (rc != MG_OK) return rc;
-  if (ld_rhs < s->ny || ld_x < s->ny) return pfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_solve_device: pitch smaller than ny");
+  if (ld_rhs < s->ny || ld_x < s->ny) return sfail(s, MG_ERR_INVALID_VALUE, "mg_pcg_solve_device: pitch smaller than ny");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   hipStream_t st = s->eng->stream;
   d_convert(dtype, MG_F64, rhs_dev, s->f, s->nx, s->ny, ld_rhs, s->ld, st);
@@ -479,8 +426,8 @@ int mg_pcg_solve(mg_pcg* s, const void* rhs, const void* u0_or_null, void* u_out
   if (rc != MG_OK) return rc;
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   hipStream_t st = s->eng->stream;
-  if ((rc = upload(s, s->f, rhs, host_dtype)) != MG_OK) return rc;
-  if (u0_or_null) { if ((rc = upload(s, s->x, u0_or_null, host_dtype)) != MG_OK) return rc; }
+  if ((rc = put(s, s->f, rhs, host_dtype)) != MG_OK) return rc;
+  if (u0_or_null) { if ((rc = put(s, s->x, u0_or_null, host_dtype)) != MG_OK) return rc; }
   else HIPC(&s->err, hipMemsetAsync(s->x, 0, field_bytes(s), st));
   if ((rc = solve_resident(s, tol, max_iter, hist, hist_cap, n_iter, converged, stats)) != MG_OK) return rc;
   return download(&s->err, u_out, host_dtype, s->x, MG_F64, s->ld, s->nx, s->ny, s->staging, st);
@@ -490,10 +437,10 @@ int mg_pcg_solve(mg_pcg* s, const void* rhs, const void* u0_or_null, void* u_out
 int mg_dev_pcg_direction(int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, const double* a_or_null,
                          const double* z, const double* p_in_or_null, double* p_out, double* q, const double* beta_dev_or_null,
                          void* scratch, double* pq_dev, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && sigma >= 0.0, "mg_dev_pcg_direction: bad shape / pitch / shift");
-  CHECK_DEV(z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_pcg_direction: NULL pointer");
-  CHECK_DEV(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null, "mg_dev_pcg_direction: p_out and q are arrays of their own");
-  CHECK_DEV(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(a_or_null), "mg_dev_pcg_direction: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && sigma >= 0.0, "mg_dev_pcg_direction: bad shape / pitch / shift");
+  CHECK_ARG(z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_pcg_direction: NULL pointer");
+  CHECK_ARG(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null, "mg_dev_pcg_direction: p_out and q are arrays of their own");
+  CHECK_ARG(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(a_or_null), "mg_dev_pcg_direction: unaligned pointer");
   const int n = launch_direction(z, beta_dev_or_null ? p_in_or_null : nullptr, p_out, q, a_or_null, nullptr, beta_dev_or_null,
                                  (double*)scratch, nx, ny, ld, hx, hy, coeff, sigma, (hipStream_t)stream);
   launch_reduce((double*)scratch, n, pq_dev, (hipStream_t)stream);
@@ -504,11 +451,11 @@ int mg_dev_pcg_direction(int nx, int ny, int ld, double hx, double hy, double co
 int mg_dev_pcg_direction_react(int nx, int ny, int ld, double hx, double hy, double coeff, double sigma, const double* a_or_null,
                                const double* c, const double* z, const double* p_in_or_null, double* p_out, double* q,
                                const double* beta_dev_or_null, void* scratch, double* pq_dev, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld) && sigma >= 0.0, "mg_dev_pcg_direction_react: bad shape / pitch / shift");
-  CHECK_DEV(c && z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_pcg_direction_react: NULL pointer");
-  CHECK_DEV(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null && p_out != c && q != c,
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld) && sigma >= 0.0, "mg_dev_pcg_direction_react: bad shape / pitch / shift");
+  CHECK_ARG(c && z && p_out && q && scratch && pq_dev && (!beta_dev_or_null || p_in_or_null), "mg_dev_pcg_direction_react: NULL pointer");
+  CHECK_ARG(p_out != p_in_or_null && p_out != z && q != z && q != p_out && q != p_in_or_null && p_out != c && q != c,
             "mg_dev_pcg_direction_react: p_out and q are arrays of their own");
-  CHECK_DEV(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(a_or_null) && aligned16(c),
+  CHECK_ARG(aligned16(z) && aligned16(p_out) && aligned16(q) && aligned16(p_in_or_null) && aligned16(a_or_null) && aligned16(c),
             "mg_dev_pcg_direction_react: unaligned pointer");
   const int n = launch_direction(z, beta_dev_or_null ? p_in_or_null : nullptr, p_out, q, a_or_null, c, beta_dev_or_null,
                                  (double*)scratch, nx, ny, ld, hx, hy, coeff, sigma, (hipStream_t)stream);
@@ -519,9 +466,9 @@ int mg_dev_pcg_direction_react(int nx, int ny, int ld, double hx, double hy, dou
 
 int mg_dev_pcg_update(int nx, int ny, int ld, const double* alpha_dev, const double* p, const double* q, double* x, double* r,
                       void* scratch, double* rr_dev, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_pcg_update: bad shape / pitch");
-  CHECK_DEV(alpha_dev && p && q && x && r && scratch && rr_dev && x != r, "mg_dev_pcg_update: bad pointer");
-  CHECK_DEV(aligned16(p) && aligned16(q) && aligned16(x) && aligned16(r), "mg_dev_pcg_update: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_pcg_update: bad shape / pitch");
+  CHECK_ARG(alpha_dev && p && q && x && r && scratch && rr_dev && x != r, "mg_dev_pcg_update: bad pointer");
+  CHECK_ARG(aligned16(p) && aligned16(q) && aligned16(x) && aligned16(r), "mg_dev_pcg_update: unaligned pointer");
   const int n = launch_update(alpha_dev, p, q, x, r, (double*)scratch, nx, ny, ld, (hipStream_t)stream);
   launch_reduce((double*)scratch, n, rr_dev, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
@@ -530,9 +477,9 @@ int mg_dev_pcg_update(int nx, int ny, int ld, const double* alpha_dev, const dou
 
 int mg_dev_pcg_dots(int nx, int ny, int ld, const double* r, const double* z, const double* q_or_null, void* scratch,
                     double* rz_dev, double* zq_dev, void* stream) {
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_pcg_dots: bad shape / pitch");
-  CHECK_DEV(r && z && scratch && rz_dev && (!q_or_null || zq_dev), "mg_dev_pcg_dots: bad pointer");
-  CHECK_DEV(aligned16(r) && aligned16(z) && aligned16(q_or_null), "mg_dev_pcg_dots: unaligned pointer");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_pcg_dots: bad shape / pitch");
+  CHECK_ARG(r && z && scratch && rz_dev && (!q_or_null || zq_dev), "mg_dev_pcg_dots: bad pointer");
+  CHECK_ARG(aligned16(r) && aligned16(z) && aligned16(q_or_null), "mg_dev_pcg_dots: unaligned pointer");
   const int n = launch_dots(r, z, q_or_null, (double*)scratch, 1024, nx, ny, ld, (hipStream_t)stream);   // <= 1024 workgroups, scratch >= 2048 doubles
   launch_reduce((double*)scratch, n, rz_dev, (hipStream_t)stream);
   if (q_or_null) launch_reduce((double*)scratch + 1024, n, zq_dev, (hipStream_t)stream);
@@ -541,7 +488,7 @@ int mg_dev_pcg_dots(int nx, int ny, int ld, const double* r, const double* z, co
 }
 
 int mg_dev_pcg_scalars(int op, const double* partials_a, int na, const double* partials_b, int nb, double* scalars, void* stream) {
-  CHECK_DEV(op >= mg::kPcgBeta0 && op <= mg::kPcgNormOp && partials_a && na >= 1 && nb >= 0 && (nb == 0 || partials_b) && scalars,
+  CHECK_ARG(op >= mg::kPcgBeta0 && op <= mg::kPcgNormOp && partials_a && na >= 1 && nb >= 0 && (nb == 0 || partials_b) && scalars,
             "mg_dev_pcg_scalars: bad argument");
   launch_scalars(op, partials_a, na, partials_b, nb, scalars, nullptr, 0, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());

@@ -45,40 +45,9 @@ struct mg_rd {
 
 namespace {
 
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-bool ld_ok(int ny, int ld) { return ld >= ny && ld % 2 == 0; }
-bool kind_ok(int kind) { return kind >= MG_NL_LINEAR && kind <= MG_NL_EXP; }
 bool scheme_ok(int scheme) { return scheme >= MG_HEAT_IMPLICIT_EULER && scheme <= MG_HEAT_BDF2; }
-bool kappa_ok(double kappa) { return kappa >= 0.0 && std::isfinite(kappa); }
-bool pos_finite(double x) { return x > 0.0 && std::isfinite(x); }
-// do the fields a and b (nx rows of pitch ld; b may be NULL) share an element?
-bool overlap(const double* a, const double* b, int nx, int ld) {
-  const uintptr_t n = (uintptr_t)nx * (uintptr_t)ld * sizeof(double), pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return b && pa < pb + n && pb < pa + n;
-}
-template <typename T> bool weight_ok(const T* w, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!(w[k] >= T(0)) || !std::isfinite((double)w[k])) return false;
-  return true;
-}
-template <typename T> bool coefficient_ok(const T* a, size_t n) {
-  for (size_t k = 0; k < n; ++k)
-    if (!(a[k] > T(0)) || !std::isfinite((double)a[k])) return false;
-  return true;
-}
-
-mg::TileGeom rd_geom(int nx, int ny, int ld) {
-  using S = mg::TileShape<double>;
-  mg::TileGeom g;
-  g.nx = nx; g.ny = ny; g.ld = ld;
-  g.nyv = std::min(ld, (ny + S::N - 1) / S::N * S::N);
-  g.i_org = 0;                                             // the ring rows are stored too
-  g.tiles_j = (ny + S::TJ - 1) / S::TJ;
-  g.ntiles = (nx + mg::kTI - 1) / mg::kTI * g.tiles_j;
-  return g;
-}
 // the sets of partials of the energy start `second` doubles apart (even: each starts 16-byte aligned)
-int energy_second(int nx, int ny, int ld) { return (rd_geom(nx, ny, ld).ntiles + 1) & ~1; }
+int energy_second(int nx, int ny, int ld) { return (field_geom(nx, ny, ld).ntiles + 1) & ~1; }
 
 // ---- launchers (shared by the driver and the stateless mg_dev_rd_* forms); an int result is the number of partials ----
 template <int KIND>
@@ -92,7 +61,7 @@ void launch_rhs_cn(bool var, const double* u, const double* u_prev, const double
 int launch_rhs(int scheme, int kind, int nx, int ny, int ld, double hx, double hy, double alpha, double dt, double kappa, double rho,
                const double* u, const double* u_prev, const double* src, const double* a, const double* w, double g0, double g1,
                double* out, double* partials, hipStream_t st) {
-  const mg::TileGeom g = rd_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const Coef k = coefs(hx, hy);
   mg::RdCoef c;
   c.ihx2 = k.ihx2; c.ihy2 = k.ihy2; c.diag = k.diag;
@@ -130,7 +99,7 @@ void launch_energy_kind(const double* u, const double* a, const double* w, doubl
 // the three sums of one state into sums3 (device)
 void launch_energy(int kind, int nx, int ny, int ld, double hx, double hy, const double* a, const double* w, const double* u,
                    double* partials, double* sums3, hipStream_t st) {
-  const mg::TileGeom g = rd_geom(nx, ny, ld);
+  const mg::TileGeom g = field_geom(nx, ny, ld);
   const int second = energy_second(nx, ny, ld);
   const double rx = hy / hx, ry = hx / hy;
   switch (kind) {
@@ -146,20 +115,6 @@ void launch_sum(const double* partials, int n, double* out, hipStream_t st) {
   hipLaunchKernelGGL(mg::rd_reduce_kernel, dim3(1), dim3(mg::kReduceBlock), 0, st, partials, n, 0, out);
 }
 
-int rfail(mg_rd* s, int code, const std::string& msg) { return fail(s ? &s->err : nullptr, code, msg); }
-// the Newton method's message joins the stepper's
-int nl_rc(mg_rd* s, int rc) {
-  if (rc != MG_OK) rfail(s, rc, std::string("Newton solver: ") + mg_nl_last_error(s->nl));
-  return rc;
-}
-#define NL(call) do { const int rc_ = nl_rc(s, (call)); if (rc_ != MG_OK) return rc_; } while (0)
-// a stateless device form of another unit
-int dev_rc(mg_rd* s, int rc) {
-  if (rc != MG_OK) rfail(s, rc, mg_last_error(nullptr));
-  return rc;
-}
-#define DEV(call) do { const int rc_ = dev_rc(s, (call)); if (rc_ != MG_OK) return rc_; } while (0)
-
 void release(mg_rd* s) {
   if (s->nl) { (void)mg_nl_destroy(s->nl); s->nl = nullptr; s->eng = nullptr; }      // the engine goes with its owner
   for (double** p : {&s->slot[0], &s->slot[1], &s->slot[2], &s->slot[3], &s->rhs, &s->src, &s->a, &s->w, &s->partials, &s->d_sums})
@@ -167,23 +122,11 @@ void release(mg_rd* s) {
   if (s->h_sums) { (void)hipHostFree(s->h_sums); s->h_sums = nullptr; }
 }
 
-size_t field_bytes(const mg_rd* s) { return (size_t)s->nx * s->ld * sizeof(double); }
 bool slot_ok(int k) { return k >= 0 && k < kSlots; }
 
 // host array (nx, ny) of hdt -> fp64 device field with the stepper's pitch, on the engine's stream (through its staging field)
-int upload(mg_rd* s, double* dev, const void* host, int hdt) {
-  hipStream_t st = s->eng->stream;
-  const size_t es = esize(hdt);
-  if (hdt == MG_F64) {
-    HIPC(&s->err, hipMemcpy2DAsync(dev, (size_t)s->ld * 8, host, (size_t)s->ny * 8, (size_t)s->ny * 8, s->nx, hipMemcpyHostToDevice, st));
-  } else {
-    int lds = 0;
-    (void)mg_pitch_elems(hdt, s->ny, &lds);
-    HIPC(&s->err, hipMemcpy2DAsync(s->eng->staging, (size_t)lds * es, host, (size_t)s->ny * es, (size_t)s->ny * es, s->nx, hipMemcpyHostToDevice, st));
-    DEV(mg_dev_convert(hdt, MG_F64, s->nx, s->ny, lds, s->ld, s->eng->staging, dev, st));
-  }
-  HIPC(&s->err, hipStreamSynchronize(st));      // the caller's array may go away
-  return MG_OK;
+int put(mg_rd* s, double* dev, const void* host, int hdt) {
+  return upload(&s->err, dev, MG_F64, s->ld, host, hdt, s->nx, s->ny, s->eng->staging, s->eng->stream);
 }
 
 // (re)place the optional device field *dev by the host array, or free it for NULL
@@ -194,12 +137,10 @@ int set_field(mg_rd* s, double** dev, const void* host_or_null, int hdt) {
     return MG_OK;
   }
   if (!*dev) { const int rc = alloc_zero(&s->err, (void**)dev, field_bytes(s), s->eng->stream); if (rc != MG_OK) return rc; }
-  return upload(s, *dev, host_or_null, hdt);
+  return put(s, *dev, host_or_null, hdt);
 }
 
 }  // namespace
-
-#define CHECK_DEV(cond, msg) do { if (!(cond)) return fail(nullptr, MG_ERR_INVALID_VALUE, msg); } while (0)
 
 extern "C" {
 
@@ -208,22 +149,22 @@ int mg_dev_rd_rhs(int scheme, int kind, int nx, int ny, int ld, double hx, doubl
                   double rho, const double* u, const double* u_prev_or_null, const double* src_or_null, const double* a_or_null,
                   const double* w_or_null, double g0, double g1, double* out, void* scratch, double* sumsq_dev_or_null,
                   void* stream) {
-  CHECK_DEV(scheme != MG_HEAT_EXPLICIT_EULER, "mg_dev_rd_rhs: explicit Euler is not a reaction-diffusion scheme (implicit Euler, Crank-Nicolson, BDF2)");
-  CHECK_DEV(scheme_ok(scheme), "mg_dev_rd_rhs: unknown scheme");
-  CHECK_DEV(kind_ok(kind), "mg_dev_rd_rhs: unknown nonlinearity (mg_nl_kind)");
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_rd_rhs: bad shape / pitch");
-  CHECK_DEV(pos_finite(dt) && pos_finite(alpha) && pos_finite(hx) && pos_finite(hy), "mg_dev_rd_rhs: dt, alpha and the spacings must be finite and > 0");
-  CHECK_DEV(kappa_ok(kappa) && std::isfinite(kappa / alpha), "mg_dev_rd_rhs: kappa must be finite and >= 0 (monotone nonlinearities only)");
-  CHECK_DEV(std::isfinite(rho) && std::isfinite((2.0 * rho) / alpha), "mg_dev_rd_rhs: rho must be finite");
-  CHECK_DEV(u && out && scratch, "mg_dev_rd_rhs: NULL pointer");
-  CHECK_DEV(scheme != MG_HEAT_BDF2 || u_prev_or_null, "mg_dev_rd_rhs: BDF2 needs u_prev");
+  CHECK_ARG(scheme != MG_HEAT_EXPLICIT_EULER, "mg_dev_rd_rhs: explicit Euler is not a reaction-diffusion scheme (implicit Euler, Crank-Nicolson, BDF2)");
+  CHECK_ARG(scheme_ok(scheme), "mg_dev_rd_rhs: unknown scheme");
+  CHECK_ARG(kind_ok(kind, MG_NL_LINEAR, MG_NL_EXP), "mg_dev_rd_rhs: unknown nonlinearity (mg_nl_kind)");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_rd_rhs: bad shape / pitch");
+  CHECK_ARG(pos_finite(dt) && pos_finite(alpha) && pos_finite(hx) && pos_finite(hy), "mg_dev_rd_rhs: dt, alpha and the spacings must be finite and > 0");
+  CHECK_ARG(kappa_ok(kappa) && std::isfinite(kappa / alpha), "mg_dev_rd_rhs: kappa must be finite and >= 0 (monotone nonlinearities only)");
+  CHECK_ARG(std::isfinite(rho) && std::isfinite((2.0 * rho) / alpha), "mg_dev_rd_rhs: rho must be finite");
+  CHECK_ARG(u && out && scratch, "mg_dev_rd_rhs: NULL pointer");
+  CHECK_ARG(scheme != MG_HEAT_BDF2 || u_prev_or_null, "mg_dev_rd_rhs: BDF2 needs u_prev");
   const bool cn = scheme == MG_HEAT_CRANK_NICOLSON;
   const double* prev = scheme == MG_HEAT_IMPLICIT_EULER ? nullptr : u_prev_or_null;
   const double* a = cn ? a_or_null : nullptr;
   const double* w = cn ? w_or_null : nullptr;
-  CHECK_DEV(!overlap(out, u, nx, ld) && !overlap(out, prev, nx, ld) && !overlap(out, src_or_null, nx, ld) &&
+  CHECK_ARG(!overlap(out, u, nx, ld) && !overlap(out, prev, nx, ld) && !overlap(out, src_or_null, nx, ld) &&
             !overlap(out, a, nx, ld) && !overlap(out, w, nx, ld), "mg_dev_rd_rhs: out is an array of its own (it overlaps an input)");
-  CHECK_DEV(aligned16(u) && aligned16(out) && aligned16(prev) && aligned16(src_or_null) && aligned16(a) && aligned16(w),
+  CHECK_ARG(aligned16(u) && aligned16(out) && aligned16(prev) && aligned16(src_or_null) && aligned16(a) && aligned16(w),
             "mg_dev_rd_rhs: unaligned pointer");
   const int n = launch_rhs(scheme, kind, nx, ny, ld, hx, hy, alpha, dt, kappa, rho, u, prev, src_or_null, a, w, g0, g1, out,
                            (double*)scratch, (hipStream_t)stream);
@@ -234,14 +175,14 @@ int mg_dev_rd_rhs(int scheme, int kind, int nx, int ny, int ld, double hx, doubl
 
 int mg_dev_rd_energy(int kind, int nx, int ny, int ld, double hx, double hy, const double* a_or_null, const double* w_or_null,
                      const double* u, void* scratch, double* sums3_dev, void* stream) {
-  CHECK_DEV(kind_ok(kind), "mg_dev_rd_energy: unknown nonlinearity (mg_nl_kind)");
-  CHECK_DEV(nx >= 3 && ny >= 3 && ld_ok(ny, ld), "mg_dev_rd_energy: bad shape / pitch");
-  CHECK_DEV(pos_finite(hx) && pos_finite(hy), "mg_dev_rd_energy: the spacings must be finite and > 0");
-  CHECK_DEV(u && scratch && sums3_dev, "mg_dev_rd_energy: NULL pointer");
-  CHECK_DEV(aligned16(u) && aligned16(a_or_null) && aligned16(w_or_null), "mg_dev_rd_energy: unaligned pointer");
+  CHECK_ARG(kind_ok(kind, MG_NL_LINEAR, MG_NL_EXP), "mg_dev_rd_energy: unknown nonlinearity (mg_nl_kind)");
+  CHECK_ARG(nx >= 3 && ny >= 3 && ld_ok_f64(ny, ld), "mg_dev_rd_energy: bad shape / pitch");
+  CHECK_ARG(pos_finite(hx) && pos_finite(hy), "mg_dev_rd_energy: the spacings must be finite and > 0");
+  CHECK_ARG(u && scratch && sums3_dev, "mg_dev_rd_energy: NULL pointer");
+  CHECK_ARG(aligned16(u) && aligned16(a_or_null) && aligned16(w_or_null), "mg_dev_rd_energy: unaligned pointer");
   int64_t bytes = 0;
   (void)mg_dev_scratch_bytes(nx, ny, &bytes);
-  CHECK_DEV((int64_t)sizeof(double) * 3 * energy_second(nx, ny, ld) <= bytes, "mg_dev_rd_energy: the scratch of this shape does not hold three sets of partials");
+  CHECK_ARG((int64_t)sizeof(double) * 3 * energy_second(nx, ny, ld) <= bytes, "mg_dev_rd_energy: the scratch of this shape does not hold three sets of partials");
   launch_energy(kind, nx, ny, ld, hx, hy, a_or_null, w_or_null, u, (double*)scratch, sums3_dev, (hipStream_t)stream);
   HIPC(nullptr, hipGetLastError());
   return MG_OK;
@@ -267,7 +208,7 @@ int mg_rd_create(const mg_config* cfg, double alpha, int num_cycles, int flexibl
   (void)mg_pitch_elems(MG_F64, cfg->ny, &s->ld);
   s->hx = s->eng->lv[0].hx; s->hy = s->eng->lv[0].hy;
   s->alpha = alpha;
-  auto bail = [&](int code) { release(s); const std::string m = s->err; delete s; last_error() = m; return code; };
+  auto bail = [&](int code) { return create_fail(s, release, code); };
   hipStream_t st = s->eng->stream;
   for (double** p : {&s->slot[0], &s->slot[1], &s->slot[2], &s->slot[3], &s->rhs})
     if ((rc = alloc_zero(&s->err, (void**)p, field_bytes(s), st)) != MG_OK) return bail(rc);
@@ -283,80 +224,75 @@ int mg_rd_create(const mg_config* cfg, double alpha, int num_cycles, int flexibl
 }
 
 int mg_rd_destroy(mg_rd* s) {
-  if (!s) return MG_OK;
-  (void)hipSetDevice(s->cfg.device);
-  if (s->eng && s->eng->stream) (void)hipStreamSynchronize(s->eng->stream);
-  release(s);
-  delete s;
-  return MG_OK;
+  return destroy_owned(s, s && s->eng ? s->eng->stream : nullptr, release);
 }
 
 const char* mg_rd_last_error(const mg_rd* s) { return s ? s->err.c_str() : last_error().c_str(); }
 
 int mg_rd_set_slot(mg_rd* s, int slot, const void* u_host, int host_dtype) {
-  if (!s || !u_host || !valid_dtype(host_dtype) || !slot_ok(slot)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_slot: bad argument");
+  if (!s || !u_host || !valid_dtype(host_dtype) || !slot_ok(slot)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_slot: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  return upload(s, s->slot[slot], u_host, host_dtype);
+  return put(s, s->slot[slot], u_host, host_dtype);
 }
 
 int mg_rd_get_slot(mg_rd* s, int slot, void* u_host, int host_dtype) {
-  if (!s || !u_host || !valid_dtype(host_dtype) || !slot_ok(slot)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_get_slot: bad argument");
+  if (!s || !u_host || !valid_dtype(host_dtype) || !slot_ok(slot)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_get_slot: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   return download(&s->err, u_host, host_dtype, s->slot[slot], MG_F64, s->ld, s->nx, s->ny, s->eng->staging, s->eng->stream);
 }
 
 int mg_rd_set_slot_device(mg_rd* s, int slot, const void* u_dev, int ld, int dtype) {
-  if (!s || !u_dev || !valid_dtype(dtype) || !slot_ok(slot) || ld < s->ny) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_slot_device: bad argument");
+  if (!s || !u_dev || !valid_dtype(dtype) || !slot_ok(slot) || ld < s->ny) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_slot_device: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  DEV(mg_dev_convert(dtype, MG_F64, s->nx, s->ny, ld, s->ld, u_dev, s->slot[slot], s->eng->stream));
+  OWNED(mg_dev_convert(dtype, MG_F64, s->nx, s->ny, ld, s->ld, u_dev, s->slot[slot], s->eng->stream), "", mg_last_error(nullptr));
   HIPC(&s->err, hipStreamSynchronize(s->eng->stream));
   return MG_OK;
 }
 
 int mg_rd_get_slot_device(mg_rd* s, int slot, void* u_dev, int ld, int dtype) {
-  if (!s || !u_dev || !valid_dtype(dtype) || !slot_ok(slot) || ld < s->ny) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_get_slot_device: bad argument");
+  if (!s || !u_dev || !valid_dtype(dtype) || !slot_ok(slot) || ld < s->ny) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_get_slot_device: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  DEV(mg_dev_convert(MG_F64, dtype, s->nx, s->ny, s->ld, ld, s->slot[slot], u_dev, s->eng->stream));
+  OWNED(mg_dev_convert(MG_F64, dtype, s->nx, s->ny, s->ld, ld, s->slot[slot], u_dev, s->eng->stream), "", mg_last_error(nullptr));
   HIPC(&s->err, hipStreamSynchronize(s->eng->stream));
   return MG_OK;
 }
 
 int mg_rd_set_source(mg_rd* s, const void* profile_host_or_null, int host_dtype) {
-  if (!s || !valid_dtype(host_dtype)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_source: bad argument");
+  if (!s || !valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_source: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   return set_field(s, &s->src, profile_host_or_null, host_dtype);
 }
 
 int mg_rd_set_coefficient(mg_rd* s, const void* a_host_or_null, int host_dtype) {
-  if (!s || !valid_dtype(host_dtype)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_coefficient: bad argument");
+  if (!s || !valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_coefficient: bad argument");
   if (a_host_or_null) {                                           // before any device work
     const size_t n = (size_t)s->nx * s->ny;
     const bool ok = host_dtype == MG_F32 ? coefficient_ok((const float*)a_host_or_null, n) : coefficient_ok((const double*)a_host_or_null, n);
-    if (!ok) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_coefficient: the diffusivity field must be finite and > 0 everywhere");
+    if (!ok) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_coefficient: the diffusivity field must be finite and > 0 everywhere");
   }
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  NL(mg_nl_set_coefficient(s->nl, a_host_or_null, host_dtype));
+  OWNED(mg_nl_set_coefficient(s->nl, a_host_or_null, host_dtype), "Newton solver: ", mg_nl_last_error(s->nl));
   s->lambda = -1.0;                 // the shift (and with it the reciprocal diagonals) is set again by the next step
   return set_field(s, &s->a, a_host_or_null, host_dtype);
 }
 
 int mg_rd_set_reaction(mg_rd* s, int kind, double kappa, const void* w_host_or_null, int host_dtype, double rho) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: NULL stepper");
-  if (!kind_ok(kind)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: unknown nonlinearity (mg_nl_kind)");
+  if (!kind_ok(kind, MG_NL_LINEAR, MG_NL_EXP)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: unknown nonlinearity (mg_nl_kind)");
   if (!kappa_ok(kappa) || !std::isfinite(kappa / s->alpha))
-    return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: kappa must be finite and >= 0 (monotone nonlinearities only; rho carries a term of the other sign explicitly)");
-  if (!std::isfinite(rho) || !std::isfinite((2.0 * rho) / s->alpha)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: rho must be finite");
-  if (!valid_dtype(host_dtype)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: bad dtype");
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: kappa must be finite and >= 0 (monotone nonlinearities only; rho carries a term of the other sign explicitly)");
+  if (!std::isfinite(rho) || !std::isfinite((2.0 * rho) / s->alpha)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: rho must be finite");
+  if (!valid_dtype(host_dtype)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: bad dtype");
   if (w_host_or_null) {
     const size_t n = (size_t)s->nx * s->ny;
     const bool ok = host_dtype == MG_F32 ? weight_ok((const float*)w_host_or_null, n) : weight_ok((const double*)w_host_or_null, n);
-    if (!ok) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: the weight field must be finite and >= 0 (monotone nonlinearities only)");
+    if (!ok) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_set_reaction: the weight field must be finite and >= 0 (monotone nonlinearities only)");
   }
   HIPC(&s->err, hipSetDevice(s->cfg.device));
-  NL(mg_nl_set_nonlinearity(s->nl, kind, kappa / s->alpha, w_host_or_null, host_dtype));
+  OWNED(mg_nl_set_nonlinearity(s->nl, kind, kappa / s->alpha, w_host_or_null, host_dtype), "Newton solver: ", mg_nl_last_error(s->nl));
   if (w_host_or_null) {
     if (!s->w) { const int rc = alloc_zero(&s->err, (void**)&s->w, field_bytes(s), s->eng->stream); if (rc != MG_OK) return rc; }
-    const int rc = upload(s, s->w, w_host_or_null, host_dtype);
+    const int rc = put(s, s->w, w_host_or_null, host_dtype);
     if (rc != MG_OK) return rc;
   }
   s->has_w = w_host_or_null != nullptr;
@@ -368,26 +304,26 @@ int mg_rd_set_reaction(mg_rd* s, int kind, double kappa, const void* w_host_or_n
 
 int mg_rd_set_newton_options(mg_rd* s, const mg_nl_options* opt) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_rd_set_newton_options: NULL stepper");
-  NL(mg_nl_set_options(s->nl, opt));
+  OWNED(mg_nl_set_options(s->nl, opt), "Newton solver: ", mg_nl_last_error(s->nl));
   return MG_OK;
 }
 
 int mg_rd_step(mg_rd* s, int scheme, double dt, int src, int prev, int dst, double g0, double g1, const double* edge4_or_null,
                double tol, int max_newton, mg_rd_step_info* info) {
   if (!s) return fail(nullptr, MG_ERR_INVALID_VALUE, "mg_rd_step: NULL stepper");
-  if (scheme == MG_HEAT_EXPLICIT_EULER) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: explicit Euler is not a reaction-diffusion scheme (implicit Euler, Crank-Nicolson, BDF2)");
-  if (!scheme_ok(scheme)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: unknown scheme");
-  if (!pos_finite(dt) || !pos_finite(dt * s->alpha)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: dt must be finite and > 0");
-  if (!slot_ok(src) || !slot_ok(dst) || src == dst) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: src and dst are two different slots 0..3");
+  if (scheme == MG_HEAT_EXPLICIT_EULER) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: explicit Euler is not a reaction-diffusion scheme (implicit Euler, Crank-Nicolson, BDF2)");
+  if (!scheme_ok(scheme)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: unknown scheme");
+  if (!pos_finite(dt) || !pos_finite(dt * s->alpha)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: dt must be finite and > 0");
+  if (!slot_ok(src) || !slot_ok(dst) || src == dst) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: src and dst are two different slots 0..3");
   if (scheme == MG_HEAT_BDF2) {
-    if (!slot_ok(prev) || prev == dst) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: BDF2 reads a prev slot 0..3 other than dst");
+    if (!slot_ok(prev) || prev == dst) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: BDF2 reads a prev slot 0..3 other than dst");
   } else if (scheme == MG_HEAT_CRANK_NICOLSON) {
-    if (prev != -1 && (!slot_ok(prev) || prev == dst)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: Crank-Nicolson's prev is -1 or a slot 0..3 other than dst");
+    if (prev != -1 && (!slot_ok(prev) || prev == dst)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: Crank-Nicolson's prev is -1 or a slot 0..3 other than dst");
   } else if (prev != -1) {
-    return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: prev is -1 for implicit Euler");
+    return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: prev is -1 for implicit Euler");
   }
-  if (!std::isfinite(g0) || !std::isfinite(g1)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: g0 / g1 not finite");
-  if (max_newton < 1 || !(tol == tol)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: max_newton < 1 / tol is NaN");
+  if (!std::isfinite(g0) || !std::isfinite(g1)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: g0 / g1 not finite");
+  if (max_newton < 1 || !(tol == tol)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_step: max_newton < 1 / tol is NaN");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   hipStream_t st = s->eng->stream;
   const double dta = dt * s->alpha;
@@ -398,17 +334,17 @@ int mg_rd_step(mg_rd* s, int scheme, double dt, int src, int prev, int dst, doub
   launch_sum(s->partials, np, s->d_sums, st);
   HIPC(&s->err, hipGetLastError());
   HIPC(&s->err, hipMemcpyAsync(s->h_sums, s->d_sums, sizeof(double), hipMemcpyDeviceToHost, st));
-  if (lambda != s->lambda) { NL(mg_nl_set_shift(s->nl, lambda)); s->lambda = lambda; }
+  if (lambda != s->lambda) { OWNED(mg_nl_set_shift(s->nl, lambda), "Newton solver: ", mg_nl_last_error(s->nl)); s->lambda = lambda; }
   // the Newton method iterates in place: dst := the initial iterate (src, or src with the ring of t + dt), then the solve
   HIPC(&s->err, hipMemcpyAsync(s->slot[dst], s->slot[src], field_bytes(s), hipMemcpyDeviceToDevice, st));
-  if (edge4_or_null) DEV(mg_dev_heat_ring(s->nx, s->ny, s->ld, edge4_or_null, s->slot[dst], st));
+  if (edge4_or_null) OWNED(mg_dev_heat_ring(s->nx, s->ny, s->ld, edge4_or_null, s->slot[dst], st), "", mg_last_error(nullptr));
   HIPC(&s->err, hipStreamSynchronize(st));                        // sum f^2 has arrived
   const double fnorm = std::sqrt(s->hx * s->hy * s->h_sums[0]);
   if ((int)s->norm_hist.size() < max_newton) s->norm_hist.resize(max_newton);
   int n = 0, conv = 0;
   mg_nl_stats stats;
-  NL(mg_nl_solve_device(s->nl, s->rhs, s->ld, s->slot[dst], s->ld, MG_F64, tol * std::max(1.0, fnorm), max_newton,
-                        s->norm_hist.data(), nullptr, nullptr, nullptr, max_newton, &n, &conv, &stats));
+  OWNED(mg_nl_solve_device(s->nl, s->rhs, s->ld, s->slot[dst], s->ld, MG_F64, tol * std::max(1.0, fnorm), max_newton,
+                        s->norm_hist.data(), nullptr, nullptr, nullptr, max_newton, &n, &conv, &stats), "Newton solver: ", mg_nl_last_error(s->nl));
   if (info) {
     info->lambda = lambda;
     info->rhs_norm = fnorm;
@@ -426,7 +362,7 @@ int mg_rd_step(mg_rd* s, int scheme, double dt, int src, int prev, int dst, doub
 }
 
 int mg_rd_energy(mg_rd* s, int slot, double out[4]) {
-  if (!s || !out || !slot_ok(slot)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_energy: bad argument");
+  if (!s || !out || !slot_ok(slot)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_energy: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   hipStream_t st = s->eng->stream;
   launch_energy(s->kind, s->nx, s->ny, s->ld, s->hx, s->hy, s->a, s->has_w ? s->w : nullptr, s->slot[slot], s->partials, s->d_sums, st);
@@ -439,10 +375,10 @@ int mg_rd_energy(mg_rd* s, int slot, double out[4]) {
 }
 
 int mg_rd_diff_norm(mg_rd* s, int slot_a, int slot_b, double* out) {
-  if (!s || !out || !slot_ok(slot_a) || !slot_ok(slot_b)) return rfail(s, MG_ERR_INVALID_VALUE, "mg_rd_diff_norm: bad argument");
+  if (!s || !out || !slot_ok(slot_a) || !slot_ok(slot_b)) return sfail(s, MG_ERR_INVALID_VALUE, "mg_rd_diff_norm: bad argument");
   HIPC(&s->err, hipSetDevice(s->cfg.device));
   hipStream_t st = s->eng->stream;
-  DEV(mg_dev_heat_diff_sumsq(s->nx, s->ny, s->ld, s->slot[slot_a], s->slot[slot_b], s->partials, s->d_sums, st));
+  OWNED(mg_dev_heat_diff_sumsq(s->nx, s->ny, s->ld, s->slot[slot_a], s->slot[slot_b], s->partials, s->d_sums, st), "", mg_last_error(nullptr));
   HIPC(&s->err, hipMemcpyAsync(s->h_sums, s->d_sums, sizeof(double), hipMemcpyDeviceToHost, st));
   HIPC(&s->err, hipStreamSynchronize(st));
   *out = std::sqrt(s->hx * s->hy * s->h_sums[0]);

@@ -294,6 +294,24 @@ def test_steps_equal_restatement_with_a_fixed_cycle_count(shape, smoother, omega
         assert not psi[0, :].any() and not psi[-1, :].any() and not psi[:, 0].any() and not psi[:, -1].any()
 
 
+def test_float32_host_arrays_give_the_bits_of_their_float64_values():
+    """set_forcing and set_vorticity with float32 host arrays (staged in fp32, cast to fp64 on the device) against the same
+    calls with the same values as float64: the cast is exact, so the psi solve and a step give the same bits."""
+    nx, ny = 65, 129
+    w0, F = (a.astype(np.float32) for a in _smooth_state((nx, ny), np.random.default_rng(5)))
+    out = []
+    for dt in (np.float32, np.float64):
+        with mg.VorticityStreamSolver(mg.Grid(nx, ny), 0.02, "no_slip", dict(zip(("left", "right", "bottom", "top"), SPEEDS)),
+                                      forcing=F.astype(dt), tolerance=0.0, max_cycles=2, max_levels=32) as s:
+            s.set_vorticity(w0.astype(dt))
+            w_set = s.vorticity
+            s.step(0.5 / (nx - 1))
+            out.append((w_set, s.vorticity, s.stream_function))
+    assert out[0][0][1:-1, 1:-1].tobytes() == w0.astype(np.float64)[1:-1, 1:-1].tobytes()      # the ring is the wall formula's
+    for got, want in zip(out[0], out[1]):
+        assert np.isfinite(got).all() and got.tobytes() == want.tobytes()
+
+
 # ======================================================================================================================
 # 4. the lid-driven cavity at 33^2, Re = 100, dt = h/2
 # ======================================================================================================================

@@ -263,6 +263,24 @@ def test_step_equals_restatement_with_a_fixed_cycle_count(shape, smoother, omega
                 st.step(kw.pop("scheme"), kw.pop("dt"), kw.pop("src"), kw.pop("dst"), **kw)
 
 
+def test_float32_host_arrays_give_the_bits_of_their_float64_values():
+    """set_slot, set_source and set_coefficient with float32 host arrays (staged in fp32, cast to fp64 on the device) against
+    the same calls with the same values as float64: the cast is exact, so the slot and a Crank-Nicolson step give the same bits."""
+    nx, ny = 129, 65
+    rng = np.random.default_rng(7)
+    u, S = (rng.standard_normal((nx, ny)).astype(np.float32) for _ in range(2))
+    a = (1.0 + rng.random((nx, ny))).astype(np.float32)
+    out = []
+    for dt in (np.float32, np.float64):
+        with mg.DeviceHeatStepper(nx, ny, UNIT, 0.6, 32, "jacobi", 0.8) as st:
+            st.set_slot(1, u.astype(dt)); st.set_source(S.astype(dt)); st.set_coefficient(a.astype(dt))
+            st.step(R.CN, 3e-3, 1, 2, None, 0.8, 0.7, None, False, tol=0.0, max_cycles=2)
+            out.append((st.get_slot(1), st.get_slot(2)))
+    assert out[0][0].tobytes() == u.astype(np.float64).tobytes()
+    for got, want in zip(out[0], out[1]):
+        assert np.isfinite(got).all() and got.tobytes() == want.tobytes()
+
+
 # ======================================================================================================================
 # 4. the class against what pins the host path
 # ======================================================================================================================

@@ -293,6 +293,27 @@ def test_one_step_against_the_dense_newton(shape, kind, precision):
             assert err <= bound
 
 
+def test_float32_host_arrays_give_the_bits_of_their_float64_values():
+    """mg_rd_set_coefficient, mg_rd_set_source, mg_rd_set_reaction and mg_rd_set_slot with float32 host arrays (staged in fp32,
+    cast to fp64 on the device) against the same calls with the same values as float64: the cast is exact, so the slot and a
+    Crank-Nicolson step give the same bits."""
+    nx, ny = 17, 33
+    a, w, S, u0, _ = (f.astype(np.float32) for f in _step_problem(nx, ny))
+    out = []
+    for dt, code in ((np.float32, _lib.MG_F32), (np.float64, _lib.MG_F64)):
+        fa, fw, fS, fu = (np.ascontiguousarray(f, dtype=dt) for f in (a, w, S, u0))
+        with Stepper(nx, ny, 0.3) as s:
+            s.ok(s.lib.mg_rd_set_coefficient(s.h, _lib.ptr(fa), code))
+            s.ok(s.lib.mg_rd_set_source(s.h, _lib.ptr(fS), code))
+            s.ok(s.lib.mg_rd_set_reaction(s.h, 1, 2.0, _lib.ptr(fw), code, 1.5))
+            s.ok(s.lib.mg_rd_set_slot(s.h, 1, _lib.ptr(fu), code))
+            info = s.step(CN, 0.01, 1, -1, 2, 0.7, 1.1, None, 1e-10)
+            out.append((s.get(1), s.get(2), info.newton_iterations, info.inner_iterations, info.final_residual))
+    assert out[0][0].tobytes() == u0.astype(np.float64).tobytes()
+    assert np.isfinite(out[0][1]).all() and out[0][1].tobytes() == out[1][1].tobytes()
+    assert out[0][2:] == out[1][2:]
+
+
 @pytest.mark.parametrize("precision", ["double", "single_managed"])
 def test_bdf2_run_step_by_step(precision):
     """8 steps (Crank-Nicolson, then BDF2), each compared with the reference's step from the DEVICE's own two states"""
