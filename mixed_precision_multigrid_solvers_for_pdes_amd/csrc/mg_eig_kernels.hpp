@@ -1,15 +1,15 @@
 // CDNA4 (gfx950) kernels of the block eigensolver (mg_eig.hip): LOBPCG around the multigrid cycle.  fp64 only: the block
 // vectors are always double, whatever precision the preconditioner runs in.
 //
-// A block is a run of columns, each an (nx, ld) field (layout of mg_kernels.hpp), `col_stride` elements apart.  Inner
+// Shared conventions: mg_tile.hpp.  A block is a run of columns, each an (nx, ld) field, `col_stride` elements apart.  Inner
 // products run over interior cells only: the ring and the pad columns (>= ny) of an operand are masked, never assumed to be
-// zero.  Every sum is per-workgroup partials followed by a fixed-order pass: no atomics, the same bits on every run.
+// zero.
 //
 // Per cell and call: gram reads each of its columns once (p + q words, or their union where u and v share columns), combine
 // reads p and writes q, apply reads 1 and writes 1 per column (2 with the coefficient), residual reads 2 and writes 1.
 #pragma once
 
-#include "mg_kernels.hpp"
+#include "mg_tile.hpp"
 
 namespace mg {
 
@@ -200,8 +200,8 @@ __global__ __launch_bounds__(kBlock) void eig_combine_kernel(const double* __res
 }
 
 // --------------------------------------------------------------------------------------------
-// av_c = A v_c on interior cells, 0 on the ring, column c = blockIdx.z.  The tile, its staging (only interior cells of v are
-//   read) and the operator expression are pcg_direction_kernel's with beta == nullptr and no shift: the same bits per cell.
+// av_c = A v_c on interior cells, 0 on the ring, column c = blockIdx.z: pcg_direction_kernel's q with beta == nullptr and no
+//   shift (only interior cells of v are read), the same bits per cell.
 //   Stored: exactly the cells [0, nx) x [0, ny) of av.
 // --------------------------------------------------------------------------------------------
 template <bool VAR>
@@ -213,81 +213,28 @@ __global__ __launch_bounds__(kBlock) void eig_apply_kernel(const double* __restr
   __shared__ __attribute__((aligned(16))) double sa[VAR ? S::LDS_ELEMS : S::N];
   const double* __restrict__ z = v_all + (long long)blockIdx.z * col_stride;
   double* __restrict__ q = av_all + (long long)blockIdx.z * col_stride;
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
+  const TileAt t = tile_at(g);
 
-  for (int v = threadIdx.x; v < (kTI + 2) * S::VPR; v += kBlock) {
-    const int r = v / S::VPR, c = v - r * S::VPR;
-    const int gi = i0 - 1 + r, gj = j0 - S::N + c * S::N;
-    Pack<double> o = zero_pack<double>();
-    if (gi >= 1 && gi < g.nx - 1 && gj >= 0 && gj < g.nyv) {
-      const Pack<double> zz = ldg(z + (size_t)gi * g.ld + gj);
-#pragma unroll
-      for (int e = 0; e < S::N; ++e) {
-        const bool interior = gj + e >= 1 && gj + e < g.ny - 1;
-        o.v[e] = interior ? zz.v[e] : 0.0;
-      }
-    }
-    *reinterpret_cast<Pack<double>*>(s + r * S::SJ + c * S::N) = o;
-  }
-  if (VAR) stage_tile<double>(a, sa, i0, j0, g.nx, g.nyv, g.ld);
+  stage_tile_map(s, t, g, [&](int gi, int gj) { return direction_pack(z, nullptr, 0.0, gi, gj, g); });
+  if (VAR) stage_tile<double>(a, sa, t.i0, t.j0, g.nx, g.nyv, g.ld);
   __syncthreads();
 
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
+  Rows3 u = rows3_start(s, t.lr + 1, t.lc), ar = rows3_start<VAR>(sa, t.lr + 1, t.lc);
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const int r = lr + k + 1;                       // LDS row of the centre
-    const Pack<double> up = *reinterpret_cast<const Pack<double>*>(s + (r - 1) * S::SJ + lc);
-    const Pack<double> mid = *reinterpret_cast<const Pack<double>*>(s + r * S::SJ + lc);
-    const Pack<double> dn = *reinterpret_cast<const Pack<double>*>(s + (r + 1) * S::SJ + lc);
-    const double left = s[r * S::SJ + lc - 1], right = s[r * S::SJ + lc + S::N];
-    Pack<double> aup = zero_pack<double>(), amid = aup, adn = aup;
-    double aleft = 0.0, aright = 0.0;
-    if (VAR) {
-      aup = *reinterpret_cast<const Pack<double>*>(sa + (r - 1) * S::SJ + lc);
-      amid = *reinterpret_cast<const Pack<double>*>(sa + r * S::SJ + lc);
-      adn = *reinterpret_cast<const Pack<double>*>(sa + (r + 1) * S::SJ + lc);
-      aleft = sa[r * S::SJ + lc - 1];
-      aright = sa[r * S::SJ + lc + S::N];
-    }
-    const int gi = i0 + lr + k;
+    rows3_advance(u, s, t.lr + k + 1, t.lc);
+    rows3_advance<VAR>(ar, sa, t.lr + k + 1, t.lc);
+    const int gi = t.i0 + t.lr + k;
     const bool row_in = (gi >= 1) && (gi < g.nx - 1);
     Pack<double> o;
 #pragma unroll
     for (int e = 0; e < S::N; ++e) {
-      const double w = (e == 0) ? left : mid.v[e - 1];
-      const double ea = (e == S::N - 1) ? right : mid.v[e + 1];
-      double au;
-      if (VAR) {
-        const double aw = (e == 0) ? aleft : amid.v[e - 1];
-        const double ae = (e == S::N - 1) ? aright : amid.v[e + 1];
-        const double aip = 0.5 * (amid.v[e] + adn.v[e]), aim = 0.5 * (amid.v[e] + aup.v[e]);
-        const double ajp = 0.5 * (amid.v[e] + ae), ajm = 0.5 * (amid.v[e] + aw);
-        const double sx = aip * dn.v[e] + aim * up.v[e];
-        const double sy = ajp * ea + ajm * w;
-        const double D = (aip + aim) * ihx2 + (ajp + ajm) * ihy2;
-        au = coeff * ((sx * ihx2 + sy * ihy2) - mid.v[e] * D);
-      } else {
-        au = coeff * (((dn.v[e] + up.v[e]) * ihx2 + (ea + w) * ihy2) - mid.v[e] * diag);
-      }
-      const int gj = gj0 + e;
+      const double au = coeff * lap5<VAR>(u, ar, e, ihx2, ihy2, diag, 0.0);
+      const int gj = t.gj0 + e;
       const bool interior = row_in && gj >= 1 && gj < g.ny - 1;
       o.v[e] = interior ? au : 0.0;
     }
-    if (gi < g.nx) {
-      double* qr = q + (size_t)gi * g.ld + gj0;
-      if (gj0 + S::N <= g.ny) {
-        stg(qr, o);
-      } else {
-#pragma unroll
-        for (int e = 0; e < S::N; ++e)
-          if (gj0 + e < g.ny) qr[e] = o.v[e];
-      }
-    }
+    if (gi < g.nx) store_cells<false>(q, o, gi, t.gj0, g);
   }
 }
 
@@ -342,10 +289,7 @@ __global__ __launch_bounds__(kBlock) void eig_zero_ring_kernel(double* __restric
   const int n = 2 * ny + 2 * nx;
   for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) {
     int i, j;
-    if (t < ny) { i = 0; j = t; }
-    else if (t < 2 * ny) { i = nx - 1; j = t - ny; }
-    else if (t < 2 * ny + nx) { i = t - 2 * ny; j = 0; }
-    else { i = t - 2 * ny - nx; j = ny - 1; }
+    ring_cell(t, nx, ny, i, j);
     r[(size_t)i * ld + j] = 0.0;
   }
 }

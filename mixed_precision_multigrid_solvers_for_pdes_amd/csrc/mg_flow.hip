@@ -88,7 +88,7 @@ int launch_diag(const double* psi, const double* w, double* partials, int nx, in
 
 // results: how many (workgroup b reduces partials[b n .. b n + n) into out[b]); bit b of max_mask: a maximum, not a sum
 void launch_reduce_results(const double* partials, int n, int results, int max_mask, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(mg::flow_reduce_kernel, dim3(results), dim3(mg::kReduceBlock), 0, st, partials, n, max_mask, out);
+  hipLaunchKernelGGL(mg::reduce_rows_kernel<true>, dim3(results), dim3(mg::kReduceBlock), 0, st, partials, n, n, max_mask, out);
 }
 
 void release(mg_flow* s) {

@@ -1,15 +1,13 @@
 // CDNA4 (gfx950) kernels of the device-resident vorticity / stream-function stepper (mg_flow.hip, include/mghip_flow.h):
 // 2-D incompressible flow  w_t = J(psi, w) + nu lap w + F,  -lap psi = w,  u = psi_y, v = -psi_x.  fp64 only.
 //
-// Conventions (field layout as in mg_kernels.hpp): every field is (nx, ny) with an even pitch `ld` in elements and a 16-byte
-// aligned base; i is x, j is y and contiguous.  Sums and maxima are per-workgroup partials followed by flow_reduce_kernel, a
-// fixed-order pass of one workgroup per result: no atomics, the same bits on every run.  Pad columns (>= ny) are masked out.
+// Shared conventions: mg_tile.hpp.  i is x, j is y and contiguous.
 //
 // Per step and cell: the right-hand side 5 words (psi, w, N_prev in; f, N out; one more with a forcing field), the wall ring a
 // perimeter, the right-hand side of the psi solve 3 (w_new, w_old in; w with a zero ring out), the diagnostics 2 (psi, w).
 #pragma once
 
-#include "mg_kernels.hpp"
+#include "mg_tile.hpp"
 
 namespace mg {
 
@@ -21,32 +19,6 @@ struct FlowCoef {
   double c0, c1;             // Adams-Bashforth weights: 1 + r/2, -r/2 with r = dt / dt_prev (1, 0 on a first step)
   double d12;                // 12.0 * hx * hy
 };
-
-// The maximum that keeps a NaN: fmax returns the operand that is NOT one, which would report a field that has blown up as
-// a field at rest.  Every maximum of this file -- per thread, per wave, per block, flow_reduce_kernel -- is formed with
-// it, so the result is NaN if any participating value is; for other operands it is fmax's value, bit for bit.
-__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
-
-__device__ __forceinline__ double wave_reduce_max(double x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x = nan_max(x, __shfl_down(x, o, 64));
-  return x;
-}
-// Maximum over the block of NW waves; result valid in thread 0.  `red` is >= NW doubles of LDS of its own.
-template <int NW = kBlock / 64>
-__device__ __forceinline__ double block_reduce_max(double x, double* red) {
-  x = wave_reduce_max(x);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = x;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0) {
-    t = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) t = nan_max(t, red[w]);
-  }
-  return t;
-}
 
 // one staged row of a thread's two columns with the column to either side: a[0] = j - 1, a[1], a[2] the pack, a[3] = j + 2
 struct FlowRow {
@@ -71,13 +43,13 @@ __device__ __forceinline__ FlowRow flow_row(const double* __restrict__ s, int ro
 //   J  = ((J1 + J2) + J3) / (12.0*hx*hy)                       (Arakawa 1966; a true division)
 //   N  = J + F                                                 (HAS_FORCE; else N = J)
 //   f  = (sigma*w + lap) + k*((c0*N) + (c1*N_prev))            (HAS_PREV; else f = (sigma*w + lap) + k*(c0*N), N_prev unread)
-// on interior cells, 0 on the ring of both outputs.  lap is residual_kernel's expression, ((dn + up) ihx2 + (ea + wv) ihy2) -
-// mid diag: what mg_op_apply(coeff = +1) gives, bit for bit.  The tile + 1-cell halo of psi AND w is staged in two LDS arrays
-// (2 x 18.5 KB per workgroup, as pcg_direction_kernel<true>); the Jacobian and lap run on the staged values (the halo holds
-// the corners).  partials[b] = sum f^2 of workgroup b, partials[np + b] = max(|N(p)-S(p)| + |E(p)-W(p)|) over its interior
-// cells (np = g.ntiles): the host forms cfl = dt m / (2 hx hy).
+// on interior cells, 0 on the ring of both outputs.  lap is lap5's constant-coefficient expression written on the FlowRows,
+// ((E + W) ihx2 + (N + S) ihy2) - w diag: what mg_op_apply(coeff = +1) gives, bit for bit.  The tiles of psi AND w are staged;
+// the Jacobian and lap run on the staged values (the halo holds the corners).  partials[b] = sum f^2 of workgroup b,
+// partials[np + b] = max(|N(p)-S(p)| + |E(p)-W(p)|) over its interior cells (np = g.ntiles): the host forms
+// cfl = dt m / (2 hx hy).
 //   Stored: rows 0 .. nx - 1 of f and N as whole 16-byte vectors up to column roundup(ny, 2) (a pad column there is written
-//   0).  Both outputs are arrays of their own: neighbouring workgroups read psi and w across tile edges.
+//   0).
 // --------------------------------------------------------------------------------------------
 template <bool HAS_PREV, bool HAS_FORCE>
 __global__ __launch_bounds__(kBlock) void flow_rhs_kernel(const double* __restrict__ psi, const double* __restrict__ om,
@@ -90,13 +62,8 @@ __global__ __launch_bounds__(kBlock) void flow_rhs_kernel(const double* __restri
   __shared__ __attribute__((aligned(16))) double sw[S::LDS_ELEMS];
   __shared__ double red[kBlock / 64];
   __shared__ double redm[kBlock / 64];
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
+  const TileAt t = tile_at(g);
+  const int i0 = t.i0, j0 = t.j0, gj0 = t.gj0, lr = t.lr, lc = t.lc;
 
   Pack<double> pv[S::RPT], fv[S::RPT];
 #pragma unroll
@@ -152,10 +119,10 @@ __global__ __launch_bounds__(kBlock) void flow_rhs_kernel(const double* __restri
     pu = pm; pm = pd;
     wu = wm; wm = wd;
   }
-  const double t = block_reduce_sum(acc, red);
+  const double sum = block_reduce_sum(acc, red);
   const double tm = block_reduce_max(vmax, redm);
   if (threadIdx.x == 0) {
-    partials[blockIdx.x] = t;
+    partials[blockIdx.x] = sum;
     partials[g.ntiles + blockIdx.x] = tm;
   }
 }
@@ -175,10 +142,7 @@ __global__ __launch_bounds__(kBlock) void flow_wall_kernel(double* __restrict__ 
   const int n = 2 * ny + 2 * nx;
   for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) {
     int i, j;
-    if (t < ny) { i = 0; j = t; }
-    else if (t < 2 * ny) { i = nx - 1; j = t - ny; }
-    else if (t < 2 * ny + nx) { i = t - 2 * ny; j = 0; }
-    else { i = t - 2 * ny - nx; j = ny - 1; }
+    ring_cell(t, nx, ny, i, j);
     if (t < 2 * ny && (j == 0 || j == ny - 1)) continue;      // the corners belong to the column passes
     double v = 0.0;
     if (kind == kFlowNoSlip) {
@@ -264,27 +228,6 @@ __global__ __launch_bounds__(kBlock) void flow_diag_kernel(const double* __restr
     partials[gridDim.x + blockIdx.x] = t1;
     partials[2 * gridDim.x + blockIdx.x] = tm;
   }
-}
-
-// One workgroup per result: workgroup b reduces partials[b * n .. b * n + n) into out[b], in a fixed order -- a sum
-// (heat_reduce_kernel's pattern), or a maximum where bit b of `max_mask` is set.
-__global__ __launch_bounds__(kReduceBlock) void flow_reduce_kernel(const double* __restrict__ partials, int n, int max_mask,
-                                                                   double* __restrict__ out) {
-  __shared__ double red[kReduceBlock / 64];
-  const double* p = partials + (size_t)blockIdx.x * n;
-  double t;
-  if ((max_mask >> blockIdx.x) & 1) {
-    double m = 0.0;
-    for (int i = threadIdx.x; i < n; i += kReduceBlock) m = nan_max(m, p[i]);
-    t = block_reduce_max<kReduceBlock / 64>(m, red);
-  } else {
-    double a0 = 0.0, a1 = 0.0;
-    int i = threadIdx.x;
-    for (; i + kReduceBlock < n; i += 2 * kReduceBlock) { a0 += p[i]; a1 += p[i + kReduceBlock]; }
-    for (; i < n; i += kReduceBlock) a0 += p[i];
-    t = block_reduce_sum<kReduceBlock / 64>(a0 + a1, red);
-  }
-  if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 
 }  // namespace mg

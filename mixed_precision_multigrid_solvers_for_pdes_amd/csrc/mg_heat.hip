@@ -89,7 +89,7 @@ int launch_diff(const double* a, const double* b, double* partials, int nx, int 
 }
 
 void launch_sum(const double* partials, int n, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(mg::heat_reduce_kernel, dim3(1), dim3(mg::kReduceBlock), 0, st, partials, n, out);
+  hipLaunchKernelGGL(mg::reduce_rows_kernel<false>, dim3(1), dim3(mg::kReduceBlock), 0, st, partials, n, 0, 0, out);
 }
 
 void release(mg_heat* s) {

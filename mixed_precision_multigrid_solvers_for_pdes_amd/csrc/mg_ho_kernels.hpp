@@ -10,12 +10,11 @@
 //   R:   (8.0*f + ((dn+up) + (ea+w))) / 12.0
 // with dn / up the rows i+1 / i-1 and ea / w the columns j+1 / j-1.
 //
-// Conventions as in mg_pcg_kernels.hpp: the 32 x 64 LDS tile with its one-cell halo (which already holds the four corner
-// neighbours: 4 words per cell in the direction kernel, as with the five-point operator); sums are per-workgroup partials
-// for a fixed-order pass; pad columns (>= ny) are never stored and never summed.
+// Shared conventions: mg_tile.hpp.  The one-cell halo of the staged tile already holds the four corner neighbours: 4 words per
+// cell in the direction kernel, as with the five-point operator.
 #pragma once
 
-#include "mg_kernels.hpp"
+#include "mg_tile.hpp"
 
 namespace mg {
 
@@ -24,48 +23,40 @@ struct HoArgs {
   double mcoeff;           // -coeff
 };
 
-// A4 at the LDS cells (r, lc .. lc + N) of a staged tile: rows r - 1, r, r + 1 with their left / right neighbours
+// A4 at the LDS cells (r, lc .. lc + N) of a staged tile: Rows3 with the four corner neighbours of the vector
 struct HoRows {
-  Pack<double> up, mid, dn;
-  double up_w, up_e, mid_w, mid_e, dn_w, dn_e;
+  Rows3 r;
+  double up_w, up_e, dn_w, dn_e;
 };
-__device__ __forceinline__ HoRows ho_load_rows(const double* s, int r, int lc) {
+__device__ __forceinline__ HoRows ho_start(const double* s, int r, int lc) {
   using S = TileShape<double>;
   HoRows h;
-  h.up = *reinterpret_cast<const Pack<double>*>(s + (r - 1) * S::SJ + lc);
-  h.mid = *reinterpret_cast<const Pack<double>*>(s + r * S::SJ + lc);
-  h.dn = *reinterpret_cast<const Pack<double>*>(s + (r + 1) * S::SJ + lc);
-  h.up_w = s[(r - 1) * S::SJ + lc - 1];  h.up_e = s[(r - 1) * S::SJ + lc + S::N];
-  h.mid_w = s[r * S::SJ + lc - 1];       h.mid_e = s[r * S::SJ + lc + S::N];
-  h.dn_w = s[(r + 1) * S::SJ + lc - 1];  h.dn_e = s[(r + 1) * S::SJ + lc + S::N];
+  h.r = rows3_start(s, r, lc);
+  h.r.left = s[(r - 1) * S::SJ + lc - 1];  h.r.right = s[(r - 1) * S::SJ + lc + S::N];
+  h.up_w = h.up_e = 0.0;
+  h.dn_w = s[r * S::SJ + lc - 1];          h.dn_e = s[r * S::SJ + lc + S::N];
   return h;
+}
+// the corner cells roll with the rows: rows3_advance's own loads of the centre row's neighbours are dead here
+__device__ __forceinline__ void ho_advance(HoRows& h, const double* s, int r, int lc) {
+  using S = TileShape<double>;
+  const double mid_w = h.dn_w, mid_e = h.dn_e;
+  h.up_w = h.r.left;  h.up_e = h.r.right;
+  rows3_advance(h.r, s, r, lc);
+  h.r.left = mid_w;  h.r.right = mid_e;
+  h.dn_w = s[(r + 1) * S::SJ + lc - 1];  h.dn_e = s[(r + 1) * S::SJ + lc + S::N];
 }
 __device__ __forceinline__ double ho_apply(const HoRows& h, int e, const HoArgs& c) {
   constexpr int N = VecW<double>::N;
-  const double w = (e == 0) ? h.mid_w : h.mid.v[e - 1], ea = (e == N - 1) ? h.mid_e : h.mid.v[e + 1];
-  const double dn_w = (e == 0) ? h.dn_w : h.dn.v[e - 1], dn_e = (e == N - 1) ? h.dn_e : h.dn.v[e + 1];
-  const double up_w = (e == 0) ? h.up_w : h.up.v[e - 1], up_e = (e == N - 1) ? h.up_e : h.up.v[e + 1];
-  return c.mcoeff * (((c.cC * h.mid.v[e] + c.cE * (h.dn.v[e] + h.up.v[e])) + c.cN * (ea + w)) - c.cK * ((dn_e + dn_w) + (up_e + up_w)));
-}
-
-// store the cells [gj0, gj0 + N) n [0, ny) of row gi (< nx): a whole vector, or cell by cell where the vector holds pad
-__device__ __forceinline__ void ho_store(double* __restrict__ out, const Pack<double>& o, int gi, int gj0, const TileGeom& g) {
-  constexpr int N = VecW<double>::N;
-  double* row = out + (size_t)gi * g.ld + gj0;
-  if (gj0 + N <= g.ny) {
-    stg(row, o);
-  } else {
-#pragma unroll
-    for (int e = 0; e < N; ++e)
-      if (gj0 + e < g.ny) row[e] = o.v[e];
-  }
+  const Rows3& u = h.r;
+  const double dn_w = (e == 0) ? h.dn_w : u.dn.v[e - 1], dn_e = (e == N - 1) ? h.dn_e : u.dn.v[e + 1];
+  const double up_w = (e == 0) ? h.up_w : u.up.v[e - 1], up_e = (e == N - 1) ? h.up_e : u.up.v[e + 1];
+  return c.mcoeff * (((c.cC * u.mid.v[e] + c.cE * (u.dn.v[e] + u.up.v[e])) + c.cN * (u.ea(e) + u.w(e))) - c.cK * ((dn_e + dn_w) + (up_e + up_w)));
 }
 
 // --------------------------------------------------------------------------------------------
 // p' = z + beta p  (beta == nullptr: p' = z, `p` is not read),  q = A4 p',  partials of p' . q -- pcg_direction_kernel's
-// contract with the nine-point operator.  p' is formed on the tile plus its halo while staging (0 on the ring and outside
-// the array), so the corners of the halo are p' too.  p_out is a buffer of its own (neighbouring workgroups read the old p
-// on this tile's edge).  Stored: exactly the cells [0, nx) x [0, ny) of p_out and q (0 on the ring).
+// contract with the nine-point operator: the corners of the staged halo are p' too.
 // --------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void ho_direction_kernel(const double* __restrict__ z, const double* __restrict__ p_in,
                                                               double* __restrict__ p_out, double* __restrict__ q,
@@ -74,56 +65,32 @@ __global__ __launch_bounds__(kBlock) void ho_direction_kernel(const double* __re
   using S = TileShape<double>;
   __shared__ __attribute__((aligned(16))) double s[S::LDS_ELEMS];
   __shared__ double red[kBlock / 64];
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
+  const TileAt t = tile_at(g);
   const double beta = beta_ptr ? *beta_ptr : 0.0;
 
-  for (int v = threadIdx.x; v < (kTI + 2) * S::VPR; v += kBlock) {
-    const int r = v / S::VPR, cv = v - r * S::VPR;
-    const int gi = i0 - 1 + r, gj = j0 - S::N + cv * S::N;
-    Pack<double> o = zero_pack<double>();
-    if (gi >= 1 && gi < g.nx - 1 && gj >= 0 && gj < g.nyv) {
-      const Pack<double> zz = ldg(z + (size_t)gi * g.ld + gj);
-      Pack<double> pp = zero_pack<double>();
-      if (beta_ptr) pp = ldg(p_in + (size_t)gi * g.ld + gj);
-#pragma unroll
-      for (int e = 0; e < S::N; ++e) {
-        const bool interior = gj + e >= 1 && gj + e < g.ny - 1;
-        const double pn = beta_ptr ? zz.v[e] + beta * pp.v[e] : zz.v[e];
-        o.v[e] = interior ? pn : 0.0;
-      }
-    }
-    *reinterpret_cast<Pack<double>*>(s + r * S::SJ + cv * S::N) = o;
-  }
+  stage_tile_map(s, t, g, [&](int gi, int gj) { return direction_pack(z, beta_ptr ? p_in : nullptr, beta, gi, gj, g); });
   __syncthreads();
 
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
   double acc = 0.0;
+  HoRows h = ho_start(s, t.lr + 1, t.lc);
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const HoRows h = ho_load_rows(s, lr + k + 1, lc);
-    const int gi = i0 + lr + k;
+    ho_advance(h, s, t.lr + k + 1, t.lc);
+    const int gi = t.i0 + t.lr + k;
     const bool row_in = (gi >= 1) && (gi < g.nx - 1);
     Pack<double> o;
 #pragma unroll
     for (int e = 0; e < S::N; ++e) {
       const double au = ho_apply(h, e, c);
-      const int gj = gj0 + e;
+      const int gj = t.gj0 + e;
       const bool interior = row_in && gj >= 1 && gj < g.ny - 1;
       o.v[e] = interior ? au : 0.0;
-      if (interior) acc += h.mid.v[e] * au;
+      if (interior) acc += h.r.mid.v[e] * au;
     }
-    if (gi < g.nx) {
-      ho_store(p_out, h.mid, gi, gj0, g);
-      ho_store(q, o, gi, gj0, g);
-    }
+    if (gi < g.nx) store_cells<false>(p_out, h.r.mid, q, o, gi, t.gj0, g);
   }
-  const double t = block_reduce_sum(acc, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  const double sum = block_reduce_sum(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 // --------------------------------------------------------------------------------------------
@@ -138,43 +105,38 @@ __global__ __launch_bounds__(kBlock) void ho_residual_kernel(const double* __res
   using S = TileShape<double>;
   __shared__ __attribute__((aligned(16))) double s[S::LDS_ELEMS];
   __shared__ double red[kBlock / 64];
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
+  const TileAt t = tile_at(g);
 
   Pack<double> f[S::RPT];
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const int gi = i0 + lr + k;
-    f[k] = (gi < g.nx && gj0 < g.nyv) ? ldg(rhs + (size_t)gi * g.ld + gj0) : zero_pack<double>();
+    const int gi = t.i0 + t.lr + k;
+    f[k] = (gi < g.nx && t.gj0 < g.nyv) ? ldg(rhs + (size_t)gi * g.ld + t.gj0) : zero_pack<double>();
   }
-  stage_tile<double>(x, s, i0, j0, g.nx, g.nyv, g.ld);
+  stage_tile<double>(x, s, t.i0, t.j0, g.nx, g.nyv, g.ld);
   __syncthreads();
 
   double acc = 0.0;
+  HoRows h = ho_start(s, t.lr + 1, t.lc);
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const HoRows h = ho_load_rows(s, lr + k + 1, lc);
-    const int gi = i0 + lr + k;
+    ho_advance(h, s, t.lr + k + 1, t.lc);
+    const int gi = t.i0 + t.lr + k;
     const bool row_in = (gi >= 1) && (gi < g.nx - 1);
     Pack<double> o;
 #pragma unroll
     for (int e = 0; e < S::N; ++e) {
       const double au = ho_apply(h, e, c);
-      const int gj = gj0 + e;
+      const int gj = t.gj0 + e;
       const bool interior = row_in && gj >= 1 && gj < g.ny - 1;
       const double rv = interior ? (f[k].v[e] - au) : 0.0;
       o.v[e] = rv;
       acc += rv * rv;
     }
-    if (WRITE_R && gi < g.nx) ho_store(r, o, gi, gj0, g);
+    if (WRITE_R && gi < g.nx) store_cells<false>(r, o, gi, t.gj0, g);
   }
-  const double t = block_reduce_sum(acc, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  const double sum = block_reduce_sum(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 // --------------------------------------------------------------------------------------------
@@ -184,35 +146,24 @@ __global__ __launch_bounds__(kBlock) void ho_residual_kernel(const double* __res
 __global__ __launch_bounds__(kBlock) void ho_rhs_kernel(const double* __restrict__ f, double* __restrict__ out, TileGeom g) {
   using S = TileShape<double>;
   __shared__ __attribute__((aligned(16))) double s[S::LDS_ELEMS];
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
-  stage_tile<double>(f, s, i0, j0, g.nx, g.nyv, g.ld);
+  const TileAt t = tile_at(g);
+  stage_tile<double>(f, s, t.i0, t.j0, g.nx, g.nyv, g.ld);
   __syncthreads();
+  Rows3 u = rows3_start(s, t.lr + 1, t.lc);
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const int r = lr + k + 1;
-    const Pack<double> up = *reinterpret_cast<const Pack<double>*>(s + (r - 1) * S::SJ + lc);
-    const Pack<double> mid = *reinterpret_cast<const Pack<double>*>(s + r * S::SJ + lc);
-    const Pack<double> dn = *reinterpret_cast<const Pack<double>*>(s + (r + 1) * S::SJ + lc);
-    const double left = s[r * S::SJ + lc - 1], right = s[r * S::SJ + lc + S::N];
-    const int gi = i0 + lr + k;
+    rows3_advance(u, s, t.lr + k + 1, t.lc);
+    const int gi = t.i0 + t.lr + k;
     const bool row_in = (gi >= 1) && (gi < g.nx - 1);
     Pack<double> o;
 #pragma unroll
     for (int e = 0; e < S::N; ++e) {
-      const double w = (e == 0) ? left : mid.v[e - 1];
-      const double ea = (e == S::N - 1) ? right : mid.v[e + 1];
-      const double rf = (8.0 * mid.v[e] + ((dn.v[e] + up.v[e]) + (ea + w))) / 12.0;
-      const int gj = gj0 + e;
+      const double rf = (8.0 * u.mid.v[e] + ((u.dn.v[e] + u.up.v[e]) + (u.ea(e) + u.w(e)))) / 12.0;
+      const int gj = t.gj0 + e;
       const bool interior = row_in && gj >= 1 && gj < g.ny - 1;
-      o.v[e] = interior ? rf : mid.v[e];
+      o.v[e] = interior ? rf : u.mid.v[e];
     }
-    if (gi < g.nx) ho_store(out, o, gi, gj0, g);
+    if (gi < g.nx) store_cells<false>(out, o, gi, t.gj0, g);
   }
 }
 

@@ -1,25 +1,23 @@
 // CDNA4 (gfx950) kernels of the conjugate-gradient outer loop around the multigrid cycle (mg_pcg.hip).  fp64 only: the Krylov
-// vectors are always double, whatever precision the preconditioner runs in.
+// vectors are always double, whatever precision the preconditioner runs in.  Shared conventions: mg_tile.hpp.
 //
-// Conventions (field layout as in mg_kernels.hpp): x carries the Dirichlet data on its ring and only its interior cells are
-// ever changed; the rings of r, p, q and z are zero and stay zero.  Every sum is taken as per-workgroup partials
-// (block_reduce_sum) followed by a fixed-order pass of one workgroup: no atomics, the same bits on every run.  Pad columns
-// (>= ny) are masked out of the sums and never stored.
+// x carries the Dirichlet data on its ring and only its interior cells are ever changed; the rings of r, p, q and z are zero
+// and stay zero.
 //
 // Per iteration and cell: direction 4 words (z, p in, p out, q; one more with the coefficient, one more with a reaction field), update 6 (p, q, x in/out, r in/out),
 // dots 2 (r, z; 3 with q for the flexible beta).
 #pragma once
 
-#include "mg_kernels.hpp"
+#include "mg_tile.hpp"
 
 namespace mg {
 
 // --------------------------------------------------------------------------------------------
 // p' = z + beta p  (beta == nullptr: p' = z, `p` is not read),  q = A p',  partials of p' . q -- one launch.
-//   LDS-tiled like residual_kernel: p' is formed on the tile plus its 1-cell halo while staging (one LDS array; VAR stages the
-//   coefficient next to it), the tile of p' is stored to p_out, the stencil runs on the staged p'.  p' is written to a buffer
-//   of its OWN: a neighbouring workgroup reads the old p on this tile's edge cells as its halo, so an in-place update would
-//   race across workgroups.  The operator expression is residual_kernel's / varcoef_kernel's own: q == -(f - A p') with f = 0.
+//   p' is formed on the tile plus its halo while staging (direction_pack; VAR stages the coefficient next to it), the tile
+//   of p' is stored to p_out, the stencil runs on the staged p'.  p' is written to a buffer of its OWN: a neighbouring
+//   workgroup reads the old p on this tile's edge cells as its halo, so an in-place update would race across workgroups.
+//   q == -(f - A p') of residual_kernel / varcoef_kernel with f = 0.
 //   Stored: exactly the cells [0, nx) x [0, ny) of p_out and q (0 on the ring).
 //   REACT (include/mghip_nl.h, mg_pcg_set_reaction_device): the operator is A + diag(c), q = q0 + c*p' with q0 the expression
 //   above; c is read once per cell straight into registers (its ring and pad are loaded and not used).
@@ -35,104 +33,44 @@ __global__ __launch_bounds__(kBlock) void pcg_direction_kernel(const double* __r
   __shared__ __attribute__((aligned(16))) double s[S::LDS_ELEMS];
   __shared__ __attribute__((aligned(16))) double sa[VAR ? S::LDS_ELEMS : S::N];
   __shared__ double red[kBlock / 64];
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
+  const TileAt t = tile_at(g);
   const double beta = beta_ptr ? *beta_ptr : 0.0;
 
   Pack<double> cr[REACT ? S::RPT : 1];
   if (REACT) {
-    const int cgr = threadIdx.x % S::CG, rgr = threadIdx.x / S::CG;
 #pragma unroll
     for (int k = 0; k < S::RPT; ++k) {
-      const int gi = i0 + rgr * S::RPT + k, gj = j0 + cgr * S::N;
-      cr[REACT ? k : 0] = (gi < g.nx && gj < g.nyv) ? ldg(creact + (size_t)gi * g.ld + gj) : zero_pack<double>();
+      const int gi = t.i0 + t.lr + k;
+      cr[REACT ? k : 0] = (gi < g.nx && t.gj0 < g.nyv) ? ldg(creact + (size_t)gi * g.ld + t.gj0) : zero_pack<double>();
     }
   }
 
-  for (int v = threadIdx.x; v < (kTI + 2) * S::VPR; v += kBlock) {
-    const int r = v / S::VPR, c = v - r * S::VPR;
-    const int gi = i0 - 1 + r, gj = j0 - S::N + c * S::N;
-    Pack<double> o = zero_pack<double>();
-    if (gi >= 1 && gi < g.nx - 1 && gj >= 0 && gj < g.nyv) {
-      const Pack<double> zz = ldg(z + (size_t)gi * g.ld + gj);
-      Pack<double> pp = zero_pack<double>();
-      if (beta_ptr) pp = ldg(p_in + (size_t)gi * g.ld + gj);
-#pragma unroll
-      for (int e = 0; e < S::N; ++e) {
-        const bool interior = gj + e >= 1 && gj + e < g.ny - 1;
-        const double pn = beta_ptr ? zz.v[e] + beta * pp.v[e] : zz.v[e];
-        o.v[e] = interior ? pn : 0.0;
-      }
-    }
-    *reinterpret_cast<Pack<double>*>(s + r * S::SJ + c * S::N) = o;
-  }
-  if (VAR) stage_tile<double>(a, sa, i0, j0, g.nx, g.nyv, g.ld);
+  stage_tile_map(s, t, g, [&](int gi, int gj) { return direction_pack(z, beta_ptr ? p_in : nullptr, beta, gi, gj, g); });
+  if (VAR) stage_tile<double>(a, sa, t.i0, t.j0, g.nx, g.nyv, g.ld);
   __syncthreads();
 
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
   double acc = 0.0;
+  Rows3 u = rows3_start(s, t.lr + 1, t.lc), ar = rows3_start<VAR>(sa, t.lr + 1, t.lc);
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const int r = lr + k + 1;                       // LDS row of the centre
-    const Pack<double> up = *reinterpret_cast<const Pack<double>*>(s + (r - 1) * S::SJ + lc);
-    const Pack<double> mid = *reinterpret_cast<const Pack<double>*>(s + r * S::SJ + lc);
-    const Pack<double> dn = *reinterpret_cast<const Pack<double>*>(s + (r + 1) * S::SJ + lc);
-    const double left = s[r * S::SJ + lc - 1], right = s[r * S::SJ + lc + S::N];
-    Pack<double> aup = zero_pack<double>(), amid = aup, adn = aup;
-    double aleft = 0.0, aright = 0.0;
-    if (VAR) {
-      aup = *reinterpret_cast<const Pack<double>*>(sa + (r - 1) * S::SJ + lc);
-      amid = *reinterpret_cast<const Pack<double>*>(sa + r * S::SJ + lc);
-      adn = *reinterpret_cast<const Pack<double>*>(sa + (r + 1) * S::SJ + lc);
-      aleft = sa[r * S::SJ + lc - 1];
-      aright = sa[r * S::SJ + lc + S::N];
-    }
-    const int gi = i0 + lr + k;
+    rows3_advance(u, s, t.lr + k + 1, t.lc);
+    rows3_advance<VAR>(ar, sa, t.lr + k + 1, t.lc);
+    const int gi = t.i0 + t.lr + k;
     const bool row_in = (gi >= 1) && (gi < g.nx - 1);
     Pack<double> o;
 #pragma unroll
     for (int e = 0; e < S::N; ++e) {
-      const double w = (e == 0) ? left : mid.v[e - 1];
-      const double ea = (e == S::N - 1) ? right : mid.v[e + 1];
-      double au;
-      if (VAR) {
-        const double aw = (e == 0) ? aleft : amid.v[e - 1];
-        const double ae = (e == S::N - 1) ? aright : amid.v[e + 1];
-        const double aip = 0.5 * (amid.v[e] + adn.v[e]), aim = 0.5 * (amid.v[e] + aup.v[e]);
-        const double ajp = 0.5 * (amid.v[e] + ae), ajm = 0.5 * (amid.v[e] + aw);
-        const double sx = aip * dn.v[e] + aim * up.v[e];
-        const double sy = ajp * ea + ajm * w;
-        const double D0 = (aip + aim) * ihx2 + (ajp + ajm) * ihy2;
-        const double D = (sigma != 0.0) ? D0 + sigma : D0;
-        au = coeff * ((sx * ihx2 + sy * ihy2) - mid.v[e] * D);
-      } else {
-        au = coeff * (((dn.v[e] + up.v[e]) * ihx2 + (ea + w) * ihy2) - mid.v[e] * diag);
-      }
-      if (REACT) au = au + cr[REACT ? k : 0].v[e] * mid.v[e];
-      const int gj = gj0 + e;
+      double au = coeff * lap5<VAR>(u, ar, e, ihx2, ihy2, diag, sigma);
+      if (REACT) au = au + cr[REACT ? k : 0].v[e] * u.mid.v[e];
+      const int gj = t.gj0 + e;
       const bool interior = row_in && gj >= 1 && gj < g.ny - 1;
       o.v[e] = interior ? au : 0.0;
-      if (interior) acc += mid.v[e] * au;
+      if (interior) acc += u.mid.v[e] * au;
     }
-    if (gi < g.nx) {
-      double* pr = p_out + (size_t)gi * g.ld + gj0;
-      double* qr = q + (size_t)gi * g.ld + gj0;
-      if (gj0 + S::N <= g.ny) {
-        stg(pr, mid);
-        stg(qr, o);
-      } else {
-#pragma unroll
-        for (int e = 0; e < S::N; ++e)
-          if (gj0 + e < g.ny) { pr[e] = mid.v[e]; qr[e] = o.v[e]; }
-      }
-    }
+    if (gi < g.nx) store_cells<false>(p_out, u.mid, q, o, gi, t.gj0, g);
   }
-  const double t = block_reduce_sum(acc, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  const double sum = block_reduce_sum(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 // x += alpha p,  r -= alpha q  on interior cells, partials of r . r over them.  16-byte vectors over rows 1 .. nx - 2; the
@@ -208,10 +146,7 @@ __global__ __launch_bounds__(kBlock) void pcg_zero_ring_kernel(double* __restric
   const int n = 2 * ny + 2 * nx;
   for (int t = blockIdx.x * kBlock + threadIdx.x; t < n; t += gridDim.x * kBlock) {
     int i, j;
-    if (t < ny) { i = 0; j = t; }
-    else if (t < 2 * ny) { i = nx - 1; j = t - ny; }
-    else if (t < 2 * ny + nx) { i = t - 2 * ny; j = 0; }
-    else { i = t - 2 * ny - nx; j = ny - 1; }
+    ring_cell(t, nx, ny, i, j);
     r[(size_t)i * ld + j] = 0.0;
   }
 }
@@ -232,22 +167,13 @@ struct PcgMailbox {
   unsigned long long seq;
 };
 
-// fixed-order sum of n partials by the whole workgroup (reduce_partials_kernel's pattern); valid in thread 0
-__device__ __forceinline__ double pcg_reduce_fixed(const double* __restrict__ partials, int n, double* red) {
-  double a0 = 0.0, a1 = 0.0;
-  int i = threadIdx.x;
-  for (; i + kReduceBlock < n; i += 2 * kReduceBlock) { a0 += partials[i]; a1 += partials[i + kReduceBlock]; }
-  for (; i < n; i += kReduceBlock) a0 += partials[i];
-  return block_reduce_sum<kReduceBlock / 64>(a0 + a1, red);
-}
-
 // One workgroup: reduce the partial sums of the launch before it and advance the scalar block (see the kPcg* operations).
 __global__ __launch_bounds__(kReduceBlock) void pcg_scalars_kernel(int op, const double* __restrict__ pa, int na,
                                                                    const double* __restrict__ pb, int nb, double* __restrict__ sc,
                                                                    PcgMailbox* mailbox, unsigned long long seq) {
   __shared__ double red[kReduceBlock / 64], red2[kReduceBlock / 64];
-  const double ta = pcg_reduce_fixed(pa, na, red);
-  const double tb = (nb > 0) ? pcg_reduce_fixed(pb, nb, red2) : 0.0;
+  const double ta = reduce_fixed(pa, na, red);
+  const double tb = (nb > 0) ? reduce_fixed(pb, nb, red2) : 0.0;
   if (threadIdx.x != 0) return;
   if (op == kPcgBeta0) {
     sc[kPcgRz] = ta; sc[kPcgRzOld] = ta; sc[kPcgZq] = 0.0; sc[kPcgBeta] = 0.0; sc[kPcgFlag] = 0.0;

@@ -108,11 +108,11 @@ void launch_energy(int kind, int nx, int ny, int ld, double hx, double hy, const
     case MG_NL_SINH: launch_energy_kind<mg::kRdSinh>(u, a, w, partials, g, rx, ry, second, st); break;
     default: launch_energy_kind<mg::kRdExp>(u, a, w, partials, g, rx, ry, second, st); break;
   }
-  hipLaunchKernelGGL(mg::rd_reduce_kernel, dim3(3), dim3(mg::kReduceBlock), 0, st, partials, g.ntiles, second, sums3);
+  hipLaunchKernelGGL(mg::reduce_rows_kernel<false>, dim3(3), dim3(mg::kReduceBlock), 0, st, partials, g.ntiles, second, 0, sums3);
 }
 
 void launch_sum(const double* partials, int n, double* out, hipStream_t st) {
-  hipLaunchKernelGGL(mg::rd_reduce_kernel, dim3(1), dim3(mg::kReduceBlock), 0, st, partials, n, 0, out);
+  hipLaunchKernelGGL(mg::reduce_rows_kernel<false>, dim3(1), dim3(mg::kReduceBlock), 0, st, partials, n, 0, 0, out);
 }
 
 void release(mg_rd* s) {

@@ -1,17 +1,11 @@
 // CDNA4 (gfx950) kernels of the device-resident reaction-diffusion stepper (mg_rd.hip; include/mghip_rd.h).  fp64 only.
-// Instantiated by mg_rd.hip alone.
-//
-// Conventions as in the heat stepper's and the Newton method's kernels: every field is (nx, ny) with an even pitch `ld` in
-// elements and a 16-byte aligned base; the 32 x 64 LDS tile with its one-cell halo where a stencil is evaluated; fields read
-// once per cell go straight into registers; sums are per-workgroup partials (block_reduce_sum) followed by rd_reduce_kernel,
-// a fixed-order pass of one workgroup per sum: no atomics, the same bits on every run; pad columns (>= ny) are never stored
-// and never summed.
+// Instantiated by mg_rd.hip alone.  Shared conventions: mg_tile.hpp.
 //
 // Per cell: the right-hand side 2 words (u in, f out) + u_prev, S, a, w where present (Crank-Nicolson up to 6, BDF2 3 - 4,
 // implicit Euler 2 - 3); the energy 1 word read (u) + a, w where present.
 #pragma once
 
-#include "mg_kernels.hpp"
+#include "mg_tile.hpp"
 
 namespace mg {
 
@@ -51,14 +45,13 @@ struct RdCoef {
 
 // --------------------------------------------------------------------------------------------
 // The right-hand side of one step in ONE pass, with the partials of the sum of out^2 (include/mghip_rd.h for the formulas and
-// their association).  heat_rhs_kernel's shape: one workgroup per 32 x 64 tile, 4 rows x one 16-byte vector per thread.
-//   Crank-Nicolson evaluates the operator and phi(u): tile + halo of u (VAR: and of a) staged in LDS, the stencil runs on the
-//   staged values; KIND and VAR are its template parameters alone.  Implicit Euler and BDF2 hold neither: u goes straight into
-//   registers and they are instantiated once each (KIND = linear, VAR = false).
+// their association).
+//   Crank-Nicolson evaluates the operator (lap5 without a shift) and phi(u) on the staged tile of u (VAR: and of a); KIND and
+//   VAR are its template parameters alone.  Implicit Euler and BDF2 hold neither: u goes straight into registers and they are
+//   instantiated once each (KIND = linear, VAR = false).
 //   u_prev (BDF2; Crank-Nicolson when non-null), S and w (non-null) are read once per cell into registers: nullable at run
 //   time (workgroup-uniform branches), so their presence multiplies no instantiation.
-//   Stored: exactly the cells [0, nx) x [0, ny), 0 on the ring -- a whole vector with the streaming hint (out is not read again
-//   by this launch), cell by cell where the vector holds the pad column.  `out` is an array of its own.
+//   Stored: exactly the cells [0, nx) x [0, ny), 0 on the ring, streamed (out is not read again by this launch).
 // --------------------------------------------------------------------------------------------
 template <int SCHEME, int KIND, bool VAR>
 __global__ __launch_bounds__(kBlock) void rd_rhs_kernel(const double* __restrict__ u, const double* __restrict__ u_prev,
@@ -71,90 +64,49 @@ __global__ __launch_bounds__(kBlock) void rd_rhs_kernel(const double* __restrict
   __shared__ __attribute__((aligned(16))) double s[CN ? S::LDS_ELEMS : S::N];
   __shared__ __attribute__((aligned(16))) double sa[VAR ? S::LDS_ELEMS : S::N];
   __shared__ double red[kBlock / 64];
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
+  const TileAt t = tile_at(g);
   const bool has_prev = SCHEME == kRdBdf2 || (CN && u_prev != nullptr);
   const bool has_w = CN && w != nullptr;
 
   Pack<double> sv[S::RPT], pv[S::RPT], wv[S::RPT], uv[S::RPT];
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const int gi = i0 + lr + k;
-    const bool in = gi < g.nx && gj0 < g.nyv;
-    const size_t at = (size_t)gi * g.ld + gj0;
+    const int gi = t.i0 + t.lr + k;
+    const bool in = gi < g.nx && t.gj0 < g.nyv;
+    const size_t at = (size_t)gi * g.ld + t.gj0;
     sv[k] = (src && in) ? ldg(src + at) : zero_pack<double>();
     pv[k] = (has_prev && in) ? ldg(u_prev + at) : zero_pack<double>();
     wv[k] = (has_w && in) ? ldg(w + at) : zero_pack<double>();
     uv[k] = (!CN && in) ? ldg(u + at) : zero_pack<double>();
   }
   if (CN) {
-    stage_tile<double>(u, s, i0, j0, g.nx, g.nyv, g.ld);
-    if (VAR) stage_tile<double>(a, sa, i0, j0, g.nx, g.nyv, g.ld);
+    stage_tile<double>(u, s, t.i0, t.j0, g.nx, g.nyv, g.ld);
+    if (VAR) stage_tile<double>(a, sa, t.i0, t.j0, g.nx, g.nyv, g.ld);
     __syncthreads();
   }
 
-  Pack<double> up = zero_pack<double>(), mid = up, aup = up, amid = up;
-  if (CN) {
-    up = *reinterpret_cast<const Pack<double>*>(s + (lr + 0) * S::SJ + lc);
-    mid = *reinterpret_cast<const Pack<double>*>(s + (lr + 1) * S::SJ + lc);
-  }
-  if (VAR) {
-    aup = *reinterpret_cast<const Pack<double>*>(sa + (lr + 0) * S::SJ + lc);
-    amid = *reinterpret_cast<const Pack<double>*>(sa + (lr + 1) * S::SJ + lc);
-  }
   double acc = 0.0;
+  Rows3 ur = rows3_start<CN>(s, t.lr + 1, t.lc), ar = rows3_start<VAR>(sa, t.lr + 1, t.lc);
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    Pack<double> dn = zero_pack<double>();
-    double left = 0.0, right = 0.0;
-    if (CN) {
-      dn = *reinterpret_cast<const Pack<double>*>(s + (lr + k + 2) * S::SJ + lc);
-      left = s[(lr + k + 1) * S::SJ + lc - 1];
-      right = s[(lr + k + 1) * S::SJ + lc + S::N];
-    } else {
-      mid = uv[k];
-    }
-    Pack<double> adn = zero_pack<double>();
-    double aleft = 0.0, aright = 0.0;
-    if (VAR) {
-      adn = *reinterpret_cast<const Pack<double>*>(sa + (lr + k + 2) * S::SJ + lc);
-      aleft = sa[(lr + k + 1) * S::SJ + lc - 1];
-      aright = sa[(lr + k + 1) * S::SJ + lc + S::N];
-    }
-    const int gi = i0 + lr + k;
+    rows3_advance<CN>(ur, s, t.lr + k + 1, t.lc);
+    rows3_advance<VAR>(ar, sa, t.lr + k + 1, t.lc);
+    if (!CN) ur.mid = uv[k];
+    const int gi = t.i0 + t.lr + k;
     const bool row_in = (gi >= 1) && (gi < g.nx - 1);
     Pack<double> o;
 #pragma unroll
     for (int e = 0; e < S::N; ++e) {
-      const int gj = gj0 + e;
+      const int gj = t.gj0 + e;
       const bool interior = row_in && gj >= 1 && gj < g.ny - 1;
-      const double uc = mid.v[e];
+      const double uc = ur.mid.v[e];
       const double sc = sv[k].v[e];                     // 0 without a source
       const double pc = pv[k].v[e];
       double val;
       if (SCHEME == kRdImplicit) {
         val = (uc + c.dt * ((c.g1 * sc) + c.rho * uc)) / c.dta;
       } else if (CN) {
-        const double we = (e == 0) ? left : mid.v[e - 1];
-        const double ea = (e == S::N - 1) ? right : mid.v[e + 1];
-        double lap;
-        if (VAR) {
-          const double aw = (e == 0) ? aleft : amid.v[e - 1];
-          const double ae = (e == S::N - 1) ? aright : amid.v[e + 1];
-          const double aip = 0.5 * (amid.v[e] + adn.v[e]), aim = 0.5 * (amid.v[e] + aup.v[e]);
-          const double ajp = 0.5 * (amid.v[e] + ae), ajm = 0.5 * (amid.v[e] + aw);
-          const double sx = aip * dn.v[e] + aim * up.v[e];
-          const double sy = ajp * ea + ajm * we;
-          const double D0 = (aip + aim) * c.ihx2 + (ajp + ajm) * c.ihy2;
-          lap = (sx * c.ihx2 + sy * c.ihy2) - uc * D0;
-        } else {
-          lap = ((dn.v[e] + up.v[e]) * c.ihx2 + (ea + we) * c.ihy2) - uc * c.diag;
-        }
+        const double lap = lap5<VAR>(ur, ar, e, c.ihx2, c.ihy2, c.diag, 0.0);
         const double h = (2.0 * ((uc + (c.dta * lap) / 2) + (c.dt * ((c.g0 * sc) + (c.g1 * sc))) / 2)) / c.dta;
         const double kw = has_w ? c.ka * wv[k].v[e] : c.ka;
         const double E = has_prev ? (3.0 * uc - pc) / 2 : uc;
@@ -166,33 +118,16 @@ __global__ __launch_bounds__(kBlock) void rd_rhs_kernel(const double* __restrict
       o.v[e] = ov;
       acc += ov * ov;
     }
-    if (gi < g.nx) {
-      double* row = out + (size_t)gi * g.ld + gj0;
-      if (gj0 + S::N <= g.ny) {
-        stg_nt(row, o);
-      } else {
-#pragma unroll
-        for (int e = 0; e < S::N; ++e)
-          if (gj0 + e < g.ny) row[e] = o.v[e];
-      }
-    }
-    if (CN) {
-      up = mid;
-      mid = dn;
-    }
-    if (VAR) {
-      aup = amid;
-      amid = adn;
-    }
+    if (gi < g.nx) store_cells<true>(out, o, gi, t.gj0, g);
   }
-  const double t = block_reduce_sum(acc, red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  const double sum = block_reduce_sum(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
 }
 
 // --------------------------------------------------------------------------------------------
 // The three sums of the free energy in ONE pass over a state (include/mghip_rd.h): G (gradient), P (potential), Q (sum of
-// squares); their partials start at partials[0], partials[second] and partials[2 * second].  Tile + halo of u (VAR: and of a)
-// staged in LDS; each cell owns the face to its next row and the face to its next column; w (non-null) is read once per cell.
+// squares); their partials start at partials[0], partials[second] and partials[2 * second].  The tile of u (VAR: and of a) is
+// staged; each cell owns the face to its next row and the face to its next column; w (non-null) is read once per cell.
 // Terms are selected, not multiplied by a mask: a non-finite cell reaches exactly the sums it enters.
 // --------------------------------------------------------------------------------------------
 template <int KIND, bool VAR>
@@ -203,50 +138,34 @@ __global__ __launch_bounds__(kBlock) void rd_energy_kernel(const double* __restr
   __shared__ __attribute__((aligned(16))) double s[S::LDS_ELEMS];
   __shared__ __attribute__((aligned(16))) double sa[VAR ? S::LDS_ELEMS : S::N];
   __shared__ double red[3][kBlock / 64];
-  const int L = xcd_remap(blockIdx.x, g.ntiles);
-  const int ti = L / g.tiles_j, tj = L - ti * g.tiles_j;
-  const int i0 = g.i_org + ti * kTI, j0 = tj * S::TJ;
-  const int cg = threadIdx.x % S::CG, rg = threadIdx.x / S::CG;
-  const int gj0 = j0 + cg * S::N;
-  const int lr = rg * S::RPT;
-  const int lc = S::N + cg * S::N;
+  const TileAt t = tile_at(g);
 
   Pack<double> wv[S::RPT];
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const int gi = i0 + lr + k;
-    wv[k] = (w && gi < g.nx && gj0 < g.nyv) ? ldg(w + (size_t)gi * g.ld + gj0) : zero_pack<double>();
+    const int gi = t.i0 + t.lr + k;
+    wv[k] = (w && gi < g.nx && t.gj0 < g.nyv) ? ldg(w + (size_t)gi * g.ld + t.gj0) : zero_pack<double>();
   }
-  stage_tile<double>(u, s, i0, j0, g.nx, g.nyv, g.ld);
-  if (VAR) stage_tile<double>(a, sa, i0, j0, g.nx, g.nyv, g.ld);
+  stage_tile<double>(u, s, t.i0, t.j0, g.nx, g.nyv, g.ld);
+  if (VAR) stage_tile<double>(a, sa, t.i0, t.j0, g.nx, g.nyv, g.ld);
   __syncthreads();
 
   double accG = 0.0, accP = 0.0, accQ = 0.0;
+  Rows3 ur = rows3_start(s, t.lr + 1, t.lc), ar = rows3_start<VAR>(sa, t.lr + 1, t.lc);
 #pragma unroll
   for (int k = 0; k < S::RPT; ++k) {
-    const int r = lr + k + 1;                       // LDS row of the centre
-    const Pack<double> mid = *reinterpret_cast<const Pack<double>*>(s + r * S::SJ + lc);
-    const Pack<double> dn = *reinterpret_cast<const Pack<double>*>(s + (r + 1) * S::SJ + lc);
-    const double right = s[r * S::SJ + lc + S::N];
-    Pack<double> amid = zero_pack<double>(), adn = amid;
-    double aright = 0.0;
-    if (VAR) {
-      amid = *reinterpret_cast<const Pack<double>*>(sa + r * S::SJ + lc);
-      adn = *reinterpret_cast<const Pack<double>*>(sa + (r + 1) * S::SJ + lc);
-      aright = sa[r * S::SJ + lc + S::N];
-    }
-    const int gi = i0 + lr + k;
+    rows3_advance(ur, s, t.lr + k + 1, t.lc);
+    rows3_advance<VAR>(ar, sa, t.lr + k + 1, t.lc);
+    const int gi = t.i0 + t.lr + k;
 #pragma unroll
     for (int e = 0; e < S::N; ++e) {
-      const int gj = gj0 + e;
-      const double uc = mid.v[e];
-      const double ea = (e == S::N - 1) ? right : mid.v[e + 1];
-      const double du = dn.v[e] - uc, dv = ea - uc;
+      const int gj = t.gj0 + e;
+      const double uc = ur.mid.v[e];
+      const double du = ur.dn.v[e] - uc, dv = ur.ea(e) - uc;
       double fx = du * du, fy = dv * dv;
       if (VAR) {
-        const double ae = (e == S::N - 1) ? aright : amid.v[e + 1];
-        fx = (0.5 * (amid.v[e] + adn.v[e])) * fx;
-        fy = (0.5 * (amid.v[e] + ae)) * fy;
+        fx = (0.5 * (ar.mid.v[e] + ar.dn.v[e])) * fx;
+        fy = (0.5 * (ar.mid.v[e] + ar.ea(e))) * fy;
       }
       const bool xface = gi < g.nx - 1 && gj >= 1 && gj < g.ny - 1;      // (gi, gj) - (gi + 1, gj)
       const bool yface = gi >= 1 && gi < g.nx - 1 && gj < g.ny - 1;      // (gi, gj) - (gi, gj + 1)
@@ -267,19 +186,6 @@ __global__ __launch_bounds__(kBlock) void rd_energy_kernel(const double* __restr
     partials[second + blockIdx.x] = t1;
     partials[2 * second + blockIdx.x] = t2;
   }
-}
-
-// Workgroup b: the fixed-order sum of the n partials that start at partials[b * stride] into out[b].
-__global__ __launch_bounds__(kReduceBlock) void rd_reduce_kernel(const double* __restrict__ partials, int n, int stride,
-                                                                 double* __restrict__ out) {
-  __shared__ double red[kReduceBlock / 64];
-  const double* p = partials + (size_t)blockIdx.x * stride;
-  double a0 = 0.0, a1 = 0.0;
-  int i = threadIdx.x;
-  for (; i + kReduceBlock < n; i += 2 * kReduceBlock) { a0 += p[i]; a1 += p[i + kReduceBlock]; }
-  for (; i < n; i += kReduceBlock) a0 += p[i];
-  const double t = block_reduce_sum<kReduceBlock / 64>(a0 + a1, red);
-  if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 
 }  // namespace mg

@@ -150,9 +150,17 @@ def test_build_lists_the_rd_unit():
             assert '"' + skipped + '"' not in text and "/" + skipped + '"' not in text, (unit, skipped)
     text = open(os.path.join(_build.CSRC, "mg_rd.hip")).read()
     assert re.findall(r'#include "([^"]+)"', text) == ["mg_host.hpp", "../../include/mghip_rd.h", "mg_rd_kernels.hpp"]
-    assert re.findall(r'#include "([^"]+)"', open(os.path.join(_build.CSRC, "mg_rd_kernels.hpp")).read()) == ["mg_kernels.hpp"]
+    assert re.findall(r'#include "([^"]+)"', open(os.path.join(_build.CSRC, "mg_rd_kernels.hpp")).read()) == ["mg_tile.hpp"]
+    assert re.findall(r'#include "([^"]+)"', open(os.path.join(_build.CSRC, "mg_tile.hpp")).read()) == ["mg_kernels.hpp"]
+    solver_units = {"mg_pcg.hip", "mg_heat.hip", "mg_rd.hip", "mg_nl.hip", "mg_eig.hip", "mg_ho.hip", "mg_flow.hip"}
+    assert "mg_tile.hpp" in hdrs
+    for unit, skip in _build.NOT_INCLUDED.items():                                # the shared helpers: the solver modules' kernel headers alone
+        assert ("mg_tile.hpp" in skip) == (unit not in solver_units), unit
+    for name in os.listdir(_build.CSRC):
+        text = open(os.path.join(_build.CSRC, name)).read()
+        assert ('#include "mg_tile.hpp"' in text) == (name[:-len("_kernels.hpp")] + ".hip" in solver_units and name.endswith("_kernels.hpp")), name
     blob = open(_build.build_library(), "rb").read()
-    for kernel in (b"rd_rhs_kernel", b"rd_energy_kernel", b"rd_reduce_kernel"):
+    for kernel in (b"rd_rhs_kernel", b"rd_energy_kernel", b"reduce_rows_kernel"):
         assert kernel in blob, kernel
 
 
