@@ -7,6 +7,7 @@ MultigridSolver, GPUMultigridSolver) plus the README facade (MixedPrecisionMulti
 PoissonProblem).  Device side: csrc/ -> lib/libmghip.so, reached through the C ABI in
 include/mghip.h.  There is no CPU fallback for the device path."""
 from .grid import Grid
+from .grid3d import Grid3D
 from .operators import (BaseOperator, DiffusionOperator, HelmholtzOperator, LaplacianOperator, ProlongationOperator,
                         RestrictionOperator)
 from .precision import PrecisionLevel, PrecisionManager
@@ -14,6 +15,7 @@ from .smoothers import (BaseSolver, ConvergenceHistory, EnhancedJacobiSolver, Ga
                         IterativeSolver, JacobiSmoother, LineRelaxationSmoother, WeightedJacobiSmoother)
 from .solver import GPUCommunicationAvoidingMultigrid, GPUMultigridSolver, MultigridCycle, MultigridSolver
 from .engine import MultigridEngine
+from .engine3d import Multigrid3DEngine
 from .gpu_kernels import MixedPrecisionKernels, SmoothingKernels, TransferKernels
 from .gpu_precision import GPUPrecisionLevel, GPUPrecisionManager
 from .memory_manager import GPUMemoryManager, GPUMemoryPool
@@ -22,7 +24,7 @@ from .facade import MixedPrecisionMultigrid, PoissonProblem, default_max_levels
 from . import applications, heat_equation
 from .heat_equation import HeatEquationConfig, HeatEquationSolver, SeparableSource, TimeSteppingScheme
 from .heat_device import DeviceHeatStepper
-from .applications import MultigridPreconditioner, PoissonSolver2D
+from .applications import MultigridPreconditioner, PoissonSolver2D, PoissonSolver3D
 from .krylov import PCGEngine, PCGSolver
 from .eigen import EigenEngine, EigenSolver
 from .flow import VorticityStreamSolver
@@ -41,6 +43,6 @@ __all__ = [
     "PoissonSolver2D", "MultigridPreconditioner", "applications", "heat_equation", "HeatEquationSolver",
     "HeatEquationConfig", "TimeSteppingScheme", "PCGEngine", "PCGSolver", "SeparableSource", "DeviceHeatStepper",
     "EigenEngine", "EigenSolver", "VorticityStreamSolver", "SemilinearEngine", "SemilinearSolver",
-    "ReactionDiffusionSolver",
+    "ReactionDiffusionSolver", "Grid3D", "Multigrid3DEngine", "PoissonSolver3D",
 ]
 __version__ = "0.1.0"

@@ -14,7 +14,10 @@ and by mg_pcg.hip, which defines mg_pcg_set_reaction_device and calls the eval k
 reaction-diffusion stepper with the kernels of mg_rd_kernels.hpp and its C header include/mghip_rd.h (which includes mghip_nl.h);
 no other unit includes either, and mg_rd.hip includes no other family's kernels: the ring fill and the difference norm are the
 heat stepper's exported device forms.  mg_tile.hpp holds what the kernels of the seven solver modules share (tile walk, five-point
-operator, masked store, ring decode, fixed-order reduce); it is included by their seven kernel headers and by nothing else."""
+operator, masked store, ring decode, fixed-order reduce); it is included by their seven kernel headers and by nothing else.
+mg_3d.hip holds the 3-D multigrid family (the engine, its stateless device forms and the kernels of mg_3d_kernels.hpp) with its C
+header include/mghip_3d.h; no other unit includes either, and mg_3d.hip includes no other family's kernels and not mg_tile.hpp: it
+takes the pitch rule through the C ABI and the fixed-order reduce from mg_kernels.hpp."""
 import os
 import shutil
 import subprocess
@@ -25,10 +28,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIBPATH = os.path.join(LIBDIR, "libmghip.so")
-SOURCES = [os.path.join(CSRC, n) for n in ("mg_launch.hip", "mg_engine.hip", "mg_solve.hip", "mg_dev.hip", "mg_plan.hip", "mg_tail.hip", "mg_pcg.hip", "mg_heat.hip", "mg_line.hip", "mg_eig.hip", "mg_ho.hip", "mg_flow.hip", "mg_nl.hip", "mg_rd.hip")]
+SOURCES = [os.path.join(CSRC, n) for n in ("mg_launch.hip", "mg_engine.hip", "mg_solve.hip", "mg_dev.hip", "mg_plan.hip", "mg_tail.hip", "mg_pcg.hip", "mg_heat.hip", "mg_line.hip", "mg_eig.hip", "mg_ho.hip", "mg_flow.hip", "mg_nl.hip", "mg_rd.hip", "mg_3d.hip")]
 HEADERS = [os.path.join(CSRC, n) for n in ("mg_kernels.hpp", "mg_tile.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp",
-                                               "mg_heat_kernels.hpp", "mg_line_kernels.hpp", "mg_eig_kernels.hpp", "mg_eig_dense.hpp", "mg_ho_kernels.hpp", "mg_flow_kernels.hpp", "mg_nl_kernels.hpp", "mg_rd_kernels.hpp")] + \
-          [os.path.join(os.path.dirname(HERE), "include", n) for n in ("mghip.h", "mghip_heat.h", "mghip_line.h", "mghip_eig.h", "mghip_ho.h", "mghip_flow.h", "mghip_nl.h", "mghip_rd.h")]
+                                               "mg_heat_kernels.hpp", "mg_line_kernels.hpp", "mg_eig_kernels.hpp", "mg_eig_dense.hpp", "mg_ho_kernels.hpp", "mg_flow_kernels.hpp", "mg_nl_kernels.hpp", "mg_rd_kernels.hpp", "mg_3d_kernels.hpp")] + \
+          [os.path.join(os.path.dirname(HERE), "include", n) for n in ("mghip.h", "mghip_heat.h", "mghip_line.h", "mghip_eig.h", "mghip_ho.h", "mghip_flow.h", "mghip_nl.h", "mghip_rd.h", "mghip_3d.h")]
 DEPS = SOURCES + HEADERS
 # headers a unit does NOT include (directly or through another header; checked against hipcc -MM): editing them leaves its
 # object current
@@ -38,20 +41,23 @@ _HO = ("mg_ho_kernels.hpp", "mghip_ho.h")                 # only mg_ho.hip inclu
 _FLOW = ("mg_flow_kernels.hpp", "mghip_flow.h")         # only mg_flow.hip includes these
 _NL = ("mg_nl_kernels.hpp", "mghip_nl.h")                 # only mg_nl.hip includes the kernel; mg_pcg.hip includes the C header too
 _RD = ("mg_rd_kernels.hpp", "mghip_rd.h")                 # only mg_rd.hip includes these (and through mghip_rd.h the Newton method's C header)
-_HOST_UNIT = ("mg_tile.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD    # mg_kernels.hpp comes with mg_host.hpp (types and constants)
-NOT_INCLUDED = {"mg_launch.hip": ("mg_tile.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD,
+_3D = ("mg_3d_kernels.hpp", "mghip_3d.h")                 # only mg_3d.hip includes these
+_HOST_UNIT = ("mg_tile.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD + _3D    # mg_kernels.hpp comes with mg_host.hpp (types and constants)
+NOT_INCLUDED = {"mg_launch.hip": ("mg_tile.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD + _3D,
                 "mg_engine.hip": _HOST_UNIT, "mg_solve.hip": _HOST_UNIT, "mg_dev.hip": _HOST_UNIT,
-                "mg_tail.hip": ("mg_tile.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD,
-                "mg_pcg.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_heat_kernels.hpp", "mg_ho_kernels.hpp", "mg_nl_kernels.hpp") + _LINE + _EIG + _FLOW + _RD,
-                "mg_heat.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD,
-                "mg_line.hip": ("mg_tile.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _EIG + _HO + _FLOW + _NL + _RD,
-                "mg_eig.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _HO + _FLOW + _NL + _RD,
-                "mg_ho.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _FLOW + _NL + _RD,
-                "mg_flow.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _NL + _RD,
-                "mg_nl.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _RD,
+                "mg_tail.hip": ("mg_tile.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD + _3D,
+                "mg_pcg.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_heat_kernels.hpp", "mg_ho_kernels.hpp", "mg_nl_kernels.hpp") + _LINE + _EIG + _FLOW + _RD + _3D,
+                "mg_heat.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _NL + _RD + _3D,
+                "mg_line.hip": ("mg_tile.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _EIG + _HO + _FLOW + _NL + _RD + _3D,
+                "mg_eig.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _HO + _FLOW + _NL + _RD + _3D,
+                "mg_ho.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _FLOW + _NL + _RD + _3D,
+                "mg_flow.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _NL + _RD + _3D,
+                "mg_nl.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _RD + _3D,
                 "mg_plan.hip": ("mg_kernels.hpp", "mg_tile.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_host.hpp", "mg_launch.hpp",
-                                "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp", "mghip_heat.h") + _LINE + _EIG + _HO + _FLOW + _NL + _RD,
-                "mg_rd.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp", "mg_nl_kernels.hpp") + _LINE + _EIG + _HO + _FLOW}
+                                "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp", "mghip_heat.h") + _LINE + _EIG + _HO + _FLOW + _NL + _RD + _3D,
+                "mg_rd.hip": ("mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp", "mg_nl_kernels.hpp") + _LINE + _EIG + _HO + _FLOW + _3D,
+                "mg_3d.hip": ("mg_tile.hpp", "mg_rb_kernels.hpp", "mg_tail_kernels.hpp", "mg_launch.hpp", "mg_pcg_kernels.hpp", "mg_heat_kernels.hpp") +
+                             _LINE + _EIG + _HO + _FLOW + _NL + _RD}
 # -ffp-contract=off: the kernels reproduce the reference's rounding sequence (no FMA contraction).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 

@@ -334,6 +334,56 @@ RD_SIGNATURES = {
     "mg_rd_diff_norm": (_i, [_vp, _i, _i, _pd]),
 }
 
+
+class Mg3Config(C.Structure):
+    """mg3_config (include/mghip_3d.h)"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("max_levels", C.c_int32),
+                ("x0", C.c_double), ("x1", C.c_double), ("y0", C.c_double), ("y1", C.c_double), ("z0", C.c_double), ("z1", C.c_double),
+                ("sigma", C.c_double), ("omega", C.c_double), ("cycle", C.c_int32), ("pre", C.c_int32), ("post", C.c_int32),
+                ("smoother", C.c_int32), ("coarse_sweeps", C.c_int32), ("precision", C.c_int32), ("device", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class Mg3Stats(C.Structure):
+    """mg3_stats (include/mghip_3d.h)"""
+    _fields_ = [("initial_residual", C.c_double), ("final_residual", C.c_double), ("solve_seconds", C.c_double),
+                ("device_bytes", C.c_int64), ("iterations", C.c_int32), ("converged", C.c_int32), ("levels", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+MG3_PREC_DOUBLE, MG3_PREC_SINGLE, MG3_PREC_DEFECT = 0, 1, 2
+MG3_PRECISIONS = {"double": MG3_PREC_DOUBLE, "single": MG3_PREC_SINGLE, "defect": MG3_PREC_DEFECT}
+
+# name -> (restype, argtypes); every symbol include/mghip_3d.h declares (the 3-D multigrid family)
+MG3_SIGNATURES = {
+    "mg3_create": (_i, [C.POINTER(Mg3Config), C.POINTER(_vp)]),
+    "mg3_destroy": (_i, [_vp]),
+    "mg3_last_error": (C.c_char_p, [_vp]),
+    "mg3_set_rhs": (_i, [_vp, _vp, _i]),
+    "mg3_set_solution": (_i, [_vp, _vp, _i]),
+    "mg3_get_solution": (_i, [_vp, _vp, _i]),
+    "mg3_set_rhs_device": (_i, [_vp, _vp, _i, _i]),
+    "mg3_set_solution_device": (_i, [_vp, _vp, _i, _i]),
+    "mg3_get_solution_device": (_i, [_vp, _vp, _i, _i]),
+    "mg3_zero_solution": (_i, [_vp]),
+    "mg3_cycle": (_i, [_vp, _i]),
+    "mg3_residual_norm": (_i, [_vp, _pd]),
+    "mg3_solve": (_i, [_vp, _d, _i, _pd, _i, _pi, _pi, C.POINTER(Mg3Stats)]),
+    "mg3_synchronize": (_i, [_vp]),
+    "mg3_stream": (_i, [_vp, C.POINTER(_vp)]),
+    "mg3_num_levels": (_i, [_vp, _pi]),
+    "mg3_device_bytes": (_i, [C.POINTER(Mg3Config), C.POINTER(C.c_int64)]),
+    "mg3_dev_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_int64)]),
+    "mg3_dev_residual": (_i, [_i] * 7 + [_d] * 4 + [_vp] * 6),
+    "mg3_dev_jacobi": (_i, [_i] * 5 + [_d] * 5 + [_vp] * 4),
+    "mg3_dev_rbgs_colour": (_i, [_i] * 5 + [_d] * 5 + [_i, _i] + [_vp] * 3),
+    "mg3_dev_restrict": (_i, [_i] * 6 + [_vp] * 3),
+    "mg3_dev_prolong_add": (_i, [_i] * 6 + [_vp] * 3),
+    "mg3_dev_upcast_add": (_i, [_i] * 5 + [_vp] * 3),
+    "mg3_dev_norm": (_i, [_i] * 5 + [_vp] * 4),
+    "mg3_dev_coarse_solve": (_i, [_i] * 5 + [_d] * 4 + [_i, _vp, _vp, _pi, _vp]),
+}
+
 _lib = None
 
 
@@ -381,7 +431,7 @@ def load():
     lib = C.CDLL(path)
     for name, (res, args) in list(SIGNATURES.items()) + list(HEAT_EXT_SIGNATURES.items()) + list(LINE_SIGNATURES.items()) + \
             list(EIG_SIGNATURES.items()) + list(HO_SIGNATURES.items()) + list(FLOW_SIGNATURES.items()) + list(NL_SIGNATURES.items()) + \
-            list(RD_SIGNATURES.items()):
+            list(RD_SIGNATURES.items()) + list(MG3_SIGNATURES.items()):
         fn = getattr(lib, name)                       # AttributeError if the ABI is incomplete
         fn.restype, fn.argtypes = res, args
     _lib = lib

@@ -7,6 +7,8 @@ end-to-end examples run on the MI355X engine:
     operator and diverges); Dirichlet data (constant or callable) goes into the boundary ring of the
     initial guess (the reference writes to a non-existent `grid.data`, poisson_solver.py:203-207); Neumann / mixed
     conditions, which the reference only sketches by patching the rhs, are rejected.
+  * PoissonSolver3D -- applications/poisson_solver.py:483-: the reference's constructor keywords (plus smoother= and precision=) and
+    PoissonSolver2D's result dict, on the 3-D engine (engine3d.py).  The reference's own solve raises NotImplementedError.
   * MultigridPreconditioner -- preconditioning/multigrid_preconditioner.py:20-176: a fixed number of cycles from a
     zero guess on the device-resident hierarchy (no convergence test), for Krylov outer loops.
 """
@@ -19,7 +21,9 @@ import numpy as np
 
 from . import _lib
 from .engine import MultigridEngine
+from .engine3d import Multigrid3DEngine, device_bytes, make_config
 from .grid import Grid
+from .grid3d import Grid3D
 from .operators import LaplacianOperator, ProlongationOperator, RestrictionOperator
 from .smoothers import GaussSeidelSmoother, JacobiSmoother
 from .solver import GPUCommunicationAvoidingMultigrid, GPUMultigridSolver, MultigridSolver
@@ -139,6 +143,120 @@ class PoissonSolver2D:
                 "expected_order": expected_order,
                 "achieved_order": {"l2": np.mean([r["l2"] for r in rates]) if rates else 0,
                                    "max": np.mean([r["max"] for r in rates]) if rates else 0}}
+
+
+class PoissonSolver3D:
+    """-laplace(u) = f on a box with Dirichlet data, on the device-resident 3-D engine.  problem.source_function and
+    problem.analytical_solution take (X, Y, Z); problem.domain holds six numbers.  precision: 'double', 'single', 'defect', or
+    None for what enable_mixed_precision says ('defect' when True, else 'double').  tolerance is relative to the norm of f, as
+    the 2-D solvers' is."""
+
+    def __init__(self, solver_type="multigrid", max_levels=5, max_iterations=100, tolerance=1e-8, cycle_type="V", use_gpu=True,
+                 device_id=0, enable_mixed_precision=True, smoother="jacobi", precision=None):
+        if solver_type not in ("multigrid", "gpu_multigrid"):
+            raise ValueError(f"Unknown solver type: {solver_type}")
+        if not use_gpu:
+            raise RuntimeError("PoissonSolver3D(use_gpu=False) is the reference's own CPU path; this package only "
+                               "provides the MI355X engine (no CPU fallback)")
+        if precision is None:
+            precision = "defect" if enable_mixed_precision else "double"
+        self.solver_type, self.max_levels = solver_type, max_levels
+        self.max_iterations, self.tolerance = max_iterations, tolerance
+        self.cycle_type, self.use_gpu, self.device_id = cycle_type, use_gpu, device_id
+        self.enable_mixed_precision, self.smoother, self.precision = enable_mixed_precision, smoother, precision
+        make_config(3, 3, 3, **self._engine_keywords())          # raises for an unknown cycle, smoother or precision
+        self.current_problem = None
+        self.solve_history: List[Dict[str, Any]] = []
+
+    def _engine_keywords(self, domain=(0.0, 1.0, 0.0, 1.0, 0.0, 1.0)):
+        return dict(domain=domain, max_levels=self.max_levels, cycle=self.cycle_type, smoother=self.smoother,
+                    precision=self.precision, device=self.device_id)
+
+    @staticmethod
+    def _boundary_guess(grid, bc):
+        """Dirichlet data -> boundary faces of the initial guess (None for homogeneous data)."""
+        if not bc:
+            return None
+        kind = bc.get("type", "dirichlet")
+        if kind != "dirichlet":
+            raise NotImplementedError(f"boundary condition type {kind!r}: the multigrid path solves Dirichlet problems")
+        value = bc.get("value", 0.0)
+        u0 = np.zeros(grid.shape)
+        if callable(value):
+            full = np.asarray(value(grid.X, grid.Y, grid.Z), dtype=np.float64)
+            for face in _faces3():
+                u0[face] = full[face]
+        elif value == 0.0:
+            return None
+        else:
+            for face in _faces3():
+                u0[face] = float(value)
+        return u0
+
+    def solve_poisson_problem_3d(self, problem, nx, ny, nz, initial_guess=None):
+        self.current_problem = problem
+        domain = tuple(float(v) for v in problem.domain)
+        if len(domain) != 6:
+            raise ValueError("a 3-D problem's domain holds six numbers (x0, x1, y0, y1, z0, z1)")
+        grid = Grid3D(nx, ny, nz, domain=domain)
+        rhs = np.ascontiguousarray(np.broadcast_to(np.asarray(problem.source_function(grid.X, grid.Y, grid.Z), dtype=np.float64), grid.shape))
+        faces = self._boundary_guess(grid, problem.boundary_conditions)
+        if initial_guess is None:
+            initial_guess = faces
+        elif faces is not None:
+            initial_guess = np.array(initial_guess, dtype=np.float64, copy=True)
+            for face in _faces3():
+                initial_guess[face] = faces[face]
+        with Multigrid3DEngine(nx, ny, nz, **self._engine_keywords(domain)) as eng:
+            eng.set_rhs(rhs)
+            eng.set_solution(initial_guess)
+            rhs_norm = float(np.sqrt(grid.hx * grid.hy * grid.hz * np.sum(rhs[grid.interior_slice()] ** 2)))
+            t0 = time.time()
+            history, converged = eng.solve(self.tolerance * (rhs_norm if rhs_norm > 0 else 1.0), self.max_iterations)
+            solve_time = time.time() - t0
+            solution = eng.solution()
+            solve_info = {"converged": converged, "iterations": len(history) - 1, "final_residual": history[-1],
+                          "residual_history": history, "levels": eng.num_levels, "precision": self.precision,
+                          "device_bytes": int(eng.last_stats.device_bytes)}
+        errors = {}
+        if problem.analytical_solution:
+            errors = self._compute_errors(solution, problem.analytical_solution(grid.X, grid.Y, grid.Z), grid)
+        results = {"problem_name": problem.name, "grid_size": (nx, ny, nz), "domain": problem.domain, "solution": solution,
+                   "solve_time": solve_time, "solver_info": solve_info, "errors": errors,
+                   "solver_type": self.solver_type, "use_gpu": self.use_gpu,
+                   "mixed_precision": self.enable_mixed_precision}
+        if problem.analytical_solution:
+            results["analytical_solution"] = problem.analytical_solution(grid.X, grid.Y, grid.Z)
+        self.solve_history.append(results)
+        return results
+
+    @staticmethod
+    def _compute_errors(numerical, analytical, grid):
+        error = numerical - analytical
+        w = grid.hx * grid.hy * grid.hz
+        l2_error = np.sqrt(np.sum(error**2) * w)
+        l2_norm = np.sqrt(np.sum(analytical**2) * w)
+        max_error = np.max(np.abs(error))
+        max_norm = np.max(np.abs(analytical))
+        gx, gy, gz = np.diff(error, axis=0) / grid.hx, np.diff(error, axis=1) / grid.hy, np.diff(error, axis=2) / grid.hz
+        h1 = np.sqrt((np.sum(gx**2) + np.sum(gy**2) + np.sum(gz**2)) * w)
+        return {"l2_error": l2_error, "relative_l2_error": l2_error / l2_norm if l2_norm > 0 else l2_error,
+                "max_error": max_error, "relative_max_error": max_error / max_norm if max_norm > 0 else max_error,
+                "h1_semi_error": h1, "grid_spacing": (grid.hx, grid.hy, grid.hz)}
+
+    def get_memory_requirements_3d(self, nx, ny, nz):
+        """what the engine allocates on the device for this hierarchy and precision (mg3_device_bytes: the same table mg3_create
+        walks), not an estimate"""
+        cfg = make_config(nx, ny, nz, **self._engine_keywords())
+        nbytes = device_bytes(cfg)
+        return {"grid_size": (nx, ny, nz), "precision": self.precision, "device_bytes": nbytes, "device_mb": nbytes / 2.0**20,
+                "device_gb": nbytes / 2.0**30, "host_bytes_per_field": int(nx) * int(ny) * int(nz) * 8}
+
+
+def _faces3():
+    """the six boundary faces of an (nx, ny, nz) array, as index tuples"""
+    a = slice(None)
+    return [(0, a, a), (-1, a, a), (a, 0, a), (a, -1, a), (a, a, 0), (a, a, -1)]
 
 
 class MultigridPreconditioner:                                         # preconditioning/multigrid_preconditioner.py:20-176

@@ -1,2 +1,3 @@
 """multigrid.core.grid (reference: src/multigrid/core/grid.py)."""
 from mixed_precision_multigrid_solvers_for_pdes_amd.grid import Grid   # noqa: F401
+from mixed_precision_multigrid_solvers_for_pdes_amd.grid3d import Grid3D   # noqa: F401
