@@ -72,7 +72,9 @@ typedef struct mg3_stats {
  * The engine.  HIERARCHY: a level is coarsened, (n + 1) / 2 per axis, while all three extents are odd and the coarse extents
  * are >= 3, up to max_levels levels.  The coarsest level is solved by coarse_sweeps red-black sweeps (colour 0 then 1,
  * omega = 1) from the zero iterate: in ONE single-workgroup launch with u and f in LDS when no extent exceeds 17, by the colour
- * kernel otherwise.  Coarse levels carry zero boundary faces.  One cycle on level l: pre sweeps, r = f - A u, coarse f =
+ * kernel otherwise.  Coarse levels carry zero boundary faces.  A hierarchy of ONE level has no coarse level: there the sweeps
+ * run in place on the caller's own iterate with its Dirichlet faces (and, for `defect`, on the fp32 correction from zero), a
+ * cycle is coarse_sweeps red-black sweeps and pre, post, omega and the smoother play no part.  One cycle on level l: pre sweeps, r = f - A u, coarse f =
  * restriction of r, coarse u = 0, one (V) or two (W) cycles on level l + 1, prolongation add, post sweeps.  A red-black sweep is
  * colour 0 then colour 1 with colour_offset 0.
  *

@@ -168,6 +168,16 @@ def defect_step(u, f, cfg):
     return out
 
 
+def defect_step_with_residual(u, r32, cfg):
+    """the defect step's second half with a GIVEN fp32 right-hand side: ONE fp32 cycle for A e = r32 from zero, u += (double)e.
+    With r32 = fp32(f - A u) it is defect_step; with the residual of an earlier f or u it models a handle whose cached residual
+    was not marked out of date"""
+    e = cycle(np.zeros(u.shape, dtype=np.float32), r32, cfg)
+    out = u.copy()
+    out[INT] = u[INT] + e[INT].astype(np.float64)
+    return out
+
+
 def solve(u, f, cfg, tol, max_iter, defect=False):
     """mg3_solve's loop: returns (u, history, converged)"""
     hist = [residual_norm(u, f, cfg)]
